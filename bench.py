@@ -5,7 +5,11 @@ One "step" = one selenite_rx_process_f32_device() call over the whole resident b
 (channels x block_size complex samples per GPU).  Inputs are generated on the device by the
 library's synthetic generator and are resident in HBM before the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, spins the clocks up, warms up, times the K steps, writes the audio of the last timed step with
+--dump-outputs and prints the result line.  --full adds everything else the line can carry (below): the per-launch and
+streaming-roof timings, the other arithmetic modes, NCO flavours and BASELINE workloads, the CPU baseline and parity.
 
 N = 1 runs in this process.  N > 1: when a launcher started this process (torch.distributed.run sets
 WORLD_SIZE / RANK / LOCAL_RANK) it is one rank of N; otherwise it starts the N ranks itself
@@ -16,8 +20,7 @@ Multi-GPU: channels shard across ranks with NO data-path collective (independent
 SURVEY.md 8e) -> weak scaling, channels per GPU fixed.  The only exchange the chain can have is the
 optional global-gain AGC (--global-gain): 4 bytes per DSP block all-reduced with MAX over RCCL.
 
-Rank 0 prints ONE JSON line (see the driver contract in the task statement) carrying `roofline`
-and, at N=1, `cpu_baseline` (the CMSIS-DSP chain timed on this box's host cores, single core and all
+Rank 0 prints ONE JSON line carrying `roofline` and, with --full at N=1, `cpu_baseline` (the CMSIS-DSP chain timed on this box's host cores, single core and all
 cores, on a bounded sample of the same workload) and `parity` (the timed arithmetic against that CMSIS chain on a
 sample of the workload, per DSP block).  Every side leg (`other_*`) gets its own clock spin-up and >= 100 launches and
 reports the MEDIAN of per-launch HIP-event durations, so the line reproduces run to run.
@@ -178,6 +181,33 @@ class _View:
 
 # vector instructions of k_cw_fused<4,2,256> per 128-sample chunk of a wavefront (profiles/r6/sq_cfg4.txt: SQ_INSTS_VALU 1.777e8 / 4096 groups / 32 chunks = 1356)
 CW_VALU_PER_CHUNK = 1360
+
+DUMP_BYTES = 32 << 20            # --dump-outputs: at most this much audio in all
+DUMP_SEED = 0x5E1E0D
+
+
+def dump_outputs(directory, d_out, channels, nout, q15, rank, world):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the audio buffer, channels x nout -- as float32
+    (int16 slots convert exactly).  Above DUMP_BYTES a fixed, seeded choice of channels (the same for every run of the same arguments)."""
+    import numpy as np
+    import selenite_rx as sr
+    rows = max(1, min(channels, DUMP_BYTES // world // (nout * 4)))
+    pick = np.arange(channels) if rows == channels else np.sort(np.random.default_rng(DUMP_SEED).choice(channels, rows, replace=False))
+    dtype = np.dtype(np.int16 if q15 else np.float32)
+    row_bytes = nout * dtype.itemsize
+    out = np.empty((rows, nout), np.float32)
+    chunk = max(1, (64 << 20) // row_bytes)                  # channels per copy to the host
+    for c0 in range(0, channels, chunk):
+        at = np.nonzero((pick >= c0) & (pick < c0 + chunk))[0]
+        if not at.size:
+            continue
+        n = int(pick[at[-1]]) + 1 - c0
+        host = np.empty((n, nout), dtype)
+        if sr.lib().selenite_rx_memcpy_d2h(host.ctypes.data, d_out.ptr + c0 * row_bytes, host.nbytes):
+            raise RuntimeError("--dump-outputs: device-to-host copy failed")
+        out[at] = host[pick[at] - c0]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "audio.npy" if world == 1 else "audio_rank%d.npy" % rank), out)
 
 
 def side_workload(name, q15, arith, spinup_ms, iters=100, rank=0, parity=True, channels_override=0, one_allocation=False):
@@ -399,12 +429,20 @@ def main():
                     help="--arith auto: 1 (the library's default) = the matrix kernel recomputes a channel it guarded itself where it can (the "
                          "no-decimator shapes: one launch per call), 3 = always k_hist_exact + the rerun pass behind it (selenite_rx_set_auto_launches; same bits)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--main-only", action="store_true", help="profiling runs: skip the cpu_baseline and other-mode legs")
+    ap.add_argument("--main-only", action="store_true", help="profiling runs with --full: only the headline's own per-launch timings, no cpu_baseline or other-mode legs")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--n1-ms", type=float, default=0.0,
                     help="ms_per_step of the SAME command at --gpus 1 (a stored figure): the N > 1 line then carries weak_scaling_efficiency = that / its own "
                          "ms_per_step (the driver computes its own from the per-N values; this is for a human running one N)")
     ap.add_argument("--n1-cfg5-ms", type=float, default=0.0, help="... and of the cfg5 shard (workloads.cfg5.ms_per_step of the N = 1 line) for cfg5_weak_scaling")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: per-launch and streaming-roof timings, the other arithmetic modes, NCO flavours and "
+                         "BASELINE workloads, cpu_baseline and parity (N = 1), the cfg5 weak-scaling leg (N > 1); --main-only / --no-cpu-baseline "
+                         "trim it as before")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the audio of the last timed step as DIR/audio.npy (float32, channels x samples; int16 "
+                         "slots converted exactly) -- at most %d MB: beyond that a fixed, seeded choice of channels, in channel order "
+                         "(N > 1: DIR/audio_rank<r>.npy, the budget split between the ranks)" % (DUMP_BYTES >> 20))
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
 
@@ -532,6 +570,13 @@ def main():
 
     env.stage("spin-up and warm-up")
     spin(step, rx.sync, args.spinup_ms)
+    if args.spinup_ms > 0:
+        # the clock ramp takes as many calls as its time allows: start the instance over and give it one fixed round of calls, so that the
+        # state the timed steps run from (and so the audio of the last one) depends on the arguments alone
+        rx.sync()
+        rx.reset()
+        for _ in range(16):
+            step()
     for _ in range(args.warmup):
         step()
     env.stage("timed steps")
@@ -551,13 +596,15 @@ def main():
     rx.check()
     env.stage("after the timed steps")
     guard = rx.guard_stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, channels, nout, q15, rank, world)
     elapsed = env.max_over_ranks(t1 - t0)
     per_rank_ms = env.gather_objects(round((t1 - t0) * 1e3 / args.steps, 4))
     devices = env.gather_objects(sr.device_pci_bus_id(local_rank))
     # per-launch durations (one HIP event between launches), after the timed region: the median SURVEY.md 8d asks for
     each = None
     roof_ms = None
-    if gg is None and rank == 0:
+    if gg is None and rank == 0 and args.full:
         each = np.sort(rx.time_process_each(d_in.ptr, d_out.ptr, bs, min(max(args.steps, 20), 200), q15))
         if not args.main_only:
             # the streaming roof of this call's traffic, measured in the same run at the same clocks: a kernel that moves the
@@ -568,7 +615,7 @@ def main():
     env.barrier()
     cfg5_line = None
     # (every run that has a process group: N > 1, and the one-rank group of SELENITE_BENCH_FORCE_DIST -- the N > 1 code path on a one-GPU box)
-    if (world > 1 or env.dist is not None) and args.workload == "cfg3" and not args.global_gain and not q15 and not args.block_size:
+    if args.full and (world > 1 or env.dist is not None) and args.workload == "cfg3" and not args.global_gain and not q15 and not args.block_size:
         env.stage("cfg5 weak-scaling leg")
         cfg5_line = cfg5_scaling_leg(env, rank, world, arith, args.steps, args.warmup, args.spinup_ms / 3.0,
                                      channels_override=2 * args.channels, n1_ms=args.n1_cfg5_ms)
@@ -666,7 +713,7 @@ def main():
         if args.n1_ms > 0:
             out["weak_scaling_efficiency"] = round(args.n1_ms / ms_per_step, 4)      # T_1 / T_N at fixed work per GPU, from the figure handed in
             out["n1_ms_per_step"] = args.n1_ms
-        if world == 1 and not args.global_gain and not args.main_only:
+        if args.full and world == 1 and not args.global_gain and not args.main_only:
             # the same workload in the other arithmetic contracts and with the general NCO flavours, outside the timed
             # region; every leg: own spin-up, >= 100 launches, median of per-launch HIP-event durations
             others = {}
@@ -718,7 +765,7 @@ def main():
                     out["auto_stopband_cost"] = dict(r, roofline_frac=frac(r), rerun_fraction=round(g1["rerun_channel_calls"] / channels, 4),
                                                      note="SELENITE_ARITH_AUTO with per-channel steps anywhere on the fs/256 grid (--nco per_channel_grid_wide): the guarded fraction of the channels "
                                                           "is recomputed by the bit-exact kernel every call")
-        if world == 1 and not args.global_gain and not args.main_only and args.workload == "cfg3" and not q15 and not args.block_size and args.arith == "auto" and args.nco == "default":
+        if args.full and world == 1 and not args.global_gain and not args.main_only and args.workload == "cfg3" and not q15 and not args.block_size and args.arith == "auto" and args.nco == "default":
             # the other single-GPU BASELINE configurations, in the same driver-run line.  The headline's batch STAYS resident (2.7 GB
             # of 288): where hipMalloc puts a workload's buffers decides which of two modes the memory system runs cfg2 in -- kernel and plain copy
             # alike, profiles/r5/placement_probe.txt -- and behind a resident allocation it has been the faster one on two boxes of three (6 of 6 runs; the third: 0 of 2); each entry carries the
@@ -741,7 +788,7 @@ def main():
                            "48 000 samples (one second per call); cfg4 = the CW chain (bit-exact in every arithmetic mode); cfg5 = the per-GPU shard of the weak-scaling "
                            "config (131 072 channels x 1024); cfg3_q15 = the headline with int16 slots in and out")
             out["workloads"] = wls
-        if world == 1 and not args.no_cpu_baseline and not args.main_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.main_only:
             out["cpu_baseline"] = cpu_baseline(args.workload, ch.WORKLOADS)
             if not args.global_gain:
                 out["parity"] = dict(parity_check(args.workload, ch.WORKLOADS, arith, q15), kernel=rx.kernel_name())

@@ -1,5 +1,6 @@
 """Shared test plumbing: ctypes views of include/selenite_rx.h, the oracle (oracle/librx_oracle.so)
-and -- in the build container only -- the real CMSIS-DSP composition (oracle/_ref/libcmsis_ref.so).
+and the real CMSIS-DSP composition (oracle/_ref/libcmsis_ref.so) -- live where it is built, its recorded
+answers (tests/golden/ref_calls.npz) everywhere else.
 
 TEST INFRASTRUCTURE.  Nothing here is imported by the product.
 """
@@ -134,27 +135,230 @@ def ref_lib():
     return _ref
 
 
+# ---------------------------------------------------------------------------------------------
+# the reference's answers where the reference is absent
+# ---------------------------------------------------------------------------------------------
+# oracle/_ref/ is compiled from the reference sources, so it exists only where they can be read.  Every call the tests
+# make into it goes through ref_call(): live where the library is built (and then checked against the committed record
+# where that holds the call), replayed from tests/golden/ref_calls.npz everywhere else.  A call is named by a digest of
+# everything that decides its answer: the primitive's arguments, or the instance's configuration and every call made on
+# it before (a running digest).  tests/golden/make_ref_calls.py writes the record.
+REF_CALLS = os.path.join(GOLDEN_DIR, "ref_calls.npz")
+_ref_record = None
+ref_calls_made = {}          # key -> tuple of arrays: the live answers of this process (what make_ref_calls.py saves)
+
+
+def _digest_update(h, part):
+    if isinstance(part, np.generic):
+        part = part.item()
+    if isinstance(part, np.ndarray):
+        a = np.ascontiguousarray(part)
+        h.update(b"A" + a.dtype.str.encode() + repr(a.shape).encode())
+        h.update(a.tobytes())
+    elif isinstance(part, dict):
+        h.update(b"D%d" % len(part))
+        for k in sorted(part):
+            _digest_update(h, k)
+            _digest_update(h, part[k])
+    elif isinstance(part, (tuple, list)):
+        h.update(b"T%d" % len(part))
+        for p in part:
+            _digest_update(h, p)
+    else:
+        h.update(b"S" + repr(part).encode() + b";")
+
+
+def digest(*parts):
+    import hashlib
+    h = hashlib.sha1()
+    _digest_update(h, parts)
+    return h.hexdigest()
+
+
+def state_digest(state):
+    """a ring's whole state (dict of arrays) as 20 bytes: what the long random traces compare step by step"""
+    return np.frombuffer(bytes.fromhex(digest(state)), np.uint8).copy()
+
+
+def spec_digest(kind, spec):
+    """everything a ChainSpec / TxSpec hands the library: sizes, flags, coefficient arrays, NCO steps, AGC / ALC parameters"""
+    return digest(kind, sorted(vars(spec).items()))
+
+
+class RecordedDigest:
+    """A recorded answer of the reference held as the digest of its dtype, shape and bits (answers the tests only compare
+    with the oracle's: chain outputs and states, ring reads, the long primitive sweeps).  identical() compares it."""
+
+    def __init__(self, hexdigest):
+        self.hex = hexdigest
+
+    def __repr__(self):
+        return "RecordedDigest(%s)" % self.hex
+
+
+def answer_digest(a):
+    return digest(np.asarray(a))
+
+
+def identical(a, b):
+    """same dtype, shape and bits (+0/-0 and NaN payloads included); either side may be a RecordedDigest"""
+    if isinstance(b, RecordedDigest):
+        a, b = b, a
+    if isinstance(a, RecordedDigest):
+        return not isinstance(b, RecordedDigest) and a.hex == answer_digest(b)
+    a, b = np.asarray(a), np.asarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def _ref_recorded():
+    global _ref_record
+    if _ref_record is None:
+        rec = {}
+        if os.path.exists(REF_CALLS):
+            with np.load(REF_CALLS) as z:
+                # "<key>_<i>": the i-th array of an answer; digest_names / digest_values: "<key>_<i>" and the digest of those held so
+                for name in z.files:
+                    if name not in ("digest_names", "digest_values"):
+                        key, i = name.rsplit("_", 1)
+                        rec.setdefault(key, {})[int(i)] = z[name]
+                for name, d in zip(z["digest_names"], z["digest_values"]):
+                    key, i = name.decode().rsplit("_", 1)
+                    rec.setdefault(key, {})[int(i)] = RecordedDigest(d.tobytes().hex())
+        _ref_record = {k: tuple(v[i] for i in range(len(v))) for k, v in rec.items()}
+    return _ref_record
+
+
+def ref_call(key, live, call, as_digest=False):
+    """The reference's answer to one call, a tuple of arrays: call() where `live` (the reference library is built), else the
+    committed record -- which holds only the digest of an answer recorded `as_digest` (replayed as RecordedDigest).  A call
+    the record does not hold is an error, never a skip."""
+    rec = _ref_recorded().get(key)
+    if live:
+        got = tuple(np.array(a, copy=True) for a in call())
+        ref_calls_made[key] = tuple(RecordedDigest(answer_digest(a)) if as_digest else a.copy() for a in got)     # (the caller may modify `got`)
+        if rec is not None:
+            assert len(rec) == len(got) and all(identical(a, b) for a, b in zip(rec, got)), \
+                "tests/golden/ref_calls.npz differs from the live reference (call %s): regenerate it (tests/golden/make_ref_calls.py)" % key
+        return got
+    if rec is None:
+        raise LookupError("tests/golden/ref_calls.npz holds no answer of the reference to this call (%s) and oracle/_ref is not built here: "
+                          "regenerate the record with tests/golden/make_ref_calls.py where the reference sources are" % key)
+    return tuple(a if isinstance(a, RecordedDigest) else a.copy() for a in rec)
+
+
+class RefLib:
+    """The primitives of oracle/_ref/libcmsis_ref.so as functions of arrays, live or recorded (ref_call).  State arrays are
+    updated in place, as the library does."""
+
+    def __init__(self):
+        self.live = ref_available()
+        self.L = ref_lib() if self.live else None
+
+    def _call(self, name, args, fn, as_digest=False):
+        return ref_call(digest("cmsis", name, args), self.live, fn, as_digest)
+
+    def sin_table(self):
+        return self._call("sin_table", (), lambda: (np.ctypeslib.as_array(self.L.ref_sin_table(), (513,)),))[0]
+
+    def sin_cos(self, x):
+        x = as_f32(x)
+
+        def live():
+            s, c = np.empty_like(x), np.empty_like(x)
+            self.L.ref_sin_cos(fptr(x), fptr(s), fptr(c), x.size)
+            return s, c
+        return self._call("sin_cos", (x,), live, as_digest=True)
+
+    def _filter(self, name, fn, args, state, nout):
+        def live():
+            y = np.empty(nout, np.float32)
+            fn(y)
+            return y, state
+        y, s = self._call(name, args + (state,), live)
+        state[...] = s
+        return y
+
+    def fir_decimate(self, c, nt, M, state, x, blk):
+        return self._filter("fir_decimate", lambda y: self.L.ref_fir_decimate(fptr(c), nt, M, fptr(state), fptr(x), fptr(y), blk),
+                            (c, nt, M, x, blk), state, blk // M)
+
+    def fir(self, c, nt, state, x, blk):
+        return self._filter("fir", lambda y: self.L.ref_fir(fptr(c), nt, fptr(state), fptr(x), fptr(y), blk), (c, nt, x, blk), state, blk)
+
+    def biquad(self, c, ns, state, x, blk):
+        return self._filter("biquad", lambda y: self.L.ref_biquad(fptr(c), ns, fptr(state), fptr(x), fptr(y), blk), (c, ns, x, blk), state, blk)
+
+    def fir_interpolate(self, c, nt, L, state, x, blk):
+        return self._filter("fir_interpolate", lambda y: self.L.ref_fir_interpolate(fptr(c), nt, L, fptr(state), fptr(x), fptr(y), blk),
+                            (c, nt, L, x, blk), state, blk * L)
+
+    def fir_decimate_init_status(self, nt, M, blk):
+        return int(self._call("fir_decimate_init_status", (nt, M, blk),
+                              lambda: (np.array(self.L.ref_fir_decimate_init_status(nt, M, blk), np.int32),))[0])
+
+    def fir_interpolate_init_status(self, nt, L, blk):
+        return int(self._call("fir_interpolate_init_status", (nt, L, blk),
+                              lambda: (np.array(self.L.ref_fir_interpolate_init_status(nt, L, blk), np.int32),))[0])
+
+    def float_to_q15_rounding(self, x):
+        """arm_float_to_q15 of the reference built with ARM_MATH_ROUNDING"""
+        x = as_f32(x)
+
+        def live():
+            q = np.empty(x.size, np.int16)
+            self.L.arm_float_to_q15_rounding(fptr(x), q.ctypes.data_as(i16p), C.c_uint32(x.size))
+            return (q,)
+        return self._call("float_to_q15_rounding", (x,), live, as_digest=True)[0]
+
+
+class _RefInstance:
+    """A stateful instance of the reference (chain or ring) behind ref_call: the key of a call is the running digest of the
+    instance's configuration and of every call made on it so far, answered or not."""
+
+    def _trail_start(self, *parts):
+        self.trail = digest(*parts)
+
+    def _step(self, name, args, fn=None):
+        self.trail = digest(self.trail, name, args)
+        if self.live and fn is not None:
+            fn()
+
+    def _ref(self, name, args, fn, as_digest=False):
+        self.trail = digest(self.trail, name, args)
+        return ref_call(self.trail, self.live, fn, as_digest)
+
+    def _ref_int(self, name, args, fn):
+        return int(self._ref(name, args, lambda: (np.array(fn(), np.int32),))[0])
+
+
 def synth_iq(first_channel, nch, first_sample, nsamp, seed=SEED):
     iq = np.empty((nch, nsamp, 2), np.float32)
     oracle_lib().orc_synth_iq(fptr(iq), first_channel, nch, first_sample, nsamp, seed)
     return iq
 
 
-class CpuChain:
-    """Oracle ('orc') or real-CMSIS composition ('ref') behind one Python face."""
+class CpuChain(_RefInstance):
+    """Oracle ('orc') or real-CMSIS composition ('ref': live or recorded, ref_call) behind one Python face."""
 
     def __init__(self, spec, which="orc"):
         self.spec, self.which = spec, which
-        self.L = oracle_lib() if which == "orc" else ref_lib()
+        self.live = which == "orc" or ref_available()
+        self.L = (oracle_lib() if which == "orc" else ref_lib()) if self.live else None
         self.h = C.c_void_p()
         self.cfg = spec.config()
-        self.rc = getattr(self.L, which + "_rx_create")(C.byref(self.h), C.byref(self.cfg))
+        if which == "ref":
+            self._trail_start(spec_digest("rx", spec))
+            self.rc = self._ref_int("create", (), lambda: self.L.ref_rx_create(C.byref(self.h), C.byref(self.cfg)))
+        else:
+            self.rc = self.L.orc_rx_create(C.byref(self.h), C.byref(self.cfg))
 
     def ok(self):
         return self.rc == 0
 
     def set_mode(self, mode):
-        return getattr(self.L, self.which + "_rx_set_mode")(self.h, mode)
+        if self.which == "ref":
+            return self._ref_int("set_mode", (mode,), lambda: self.L.ref_rx_set_mode(self.h, mode))
+        return self.L.orc_rx_set_mode(self.h, mode)
 
     def process(self, iq, nthreads=1):
         iq = as_f32(iq)
@@ -162,18 +366,26 @@ class CpuChain:
         out = np.empty((c, self.spec.out_len(bs)), np.float32)
         if self.which == "orc":
             self.L.orc_rx_process_f32(self.h, fptr(iq), fptr(out), bs, nthreads)
-        else:
+            return out
+
+        def run():
             self.L.ref_rx_process_f32(self.h, fptr(iq), fptr(out), bs)
-        return out
+            return (out,)
+        return self._ref("process_f32", (iq,), run, as_digest=True)[0]
 
     def process_env(self, iq, env_override=None):
         iq = as_f32(iq)
         c, bs = iq.shape[0], iq.shape[1]
         out = np.empty((c, self.spec.out_len(bs)), np.float32)
         env = np.empty((bs // self.spec.block,), np.float32)
-        fn = getattr(self.L, self.which + "_rx_process_f32_env")
-        fn(self.h, fptr(iq), fptr(out), bs, fptr(env_override) if env_override is not None else None, fptr(env))
-        return out, env
+
+        def run():
+            fn = getattr(self.L, self.which + "_rx_process_f32_env")
+            fn(self.h, fptr(iq), fptr(out), bs, fptr(env_override) if env_override is not None else None, fptr(env))
+            return out, env
+        if self.which == "orc":
+            return run()
+        return self._ref("process_f32_env", (iq, env_override), run, as_digest=True)
 
     def process_q15(self, iq):
         iq = np.ascontiguousarray(iq, dtype=np.int16)
@@ -181,15 +393,24 @@ class CpuChain:
         out = np.empty((c, self.spec.out_len(bs)), np.int16)
         if self.which == "orc":
             self.L.orc_rx_process_q15(self.h, iq.ctypes.data_as(i16p), out.ctypes.data_as(i16p), bs, 1)
-        else:
+            return out
+
+        def run():
             self.L.ref_rx_process_q15(self.h, iq.ctypes.data_as(i16p), out.ctypes.data_as(i16p), bs)
-        return out
+            return (out,)
+        return self._ref("process_q15", (iq,), run, as_digest=True)[0]
 
     def state(self):
         arrs = self.spec.state_arrays()
-        v = state_view(arrs)
-        getattr(self.L, self.which + "_rx_get_state")(self.h, C.byref(v))
-        return arrs
+
+        def run():
+            v = state_view(arrs)
+            getattr(self.L, self.which + "_rx_get_state")(self.h, C.byref(v))
+            return tuple(arrs[k] for k in sorted(arrs))
+        if self.which == "orc":
+            run()
+            return arrs
+        return dict(zip(sorted(arrs), self._ref("state", (), run, as_digest=True)))
 
     def close(self):
         if self.h:
@@ -247,31 +468,38 @@ def ring_ref_available():
     return os.path.exists(os.path.join(REF_DIR, "libdsp_if_ref.so"))
 
 
-class RefRing:
-    """The reference's OWN ring-buffer code (Core/Src/dsp_if.c:116-340 compiled from /root/reference into
-    oracle/_ref/libdsp_if_ref.so by oracle/Makefile) behind the Python face of selenite_rx.Ring.  The firmware has
+class RefRing(_RefInstance):
+    """The reference's OWN ring-buffer code (Core/Src/dsp_if.c:116-340 compiled from the reference sources into
+    oracle/_ref/libdsp_if_ref.so by oracle/Makefile) behind the Python face of selenite_rx.Ring -- live, or recorded
+    (ref_call) where that library is not built.  The firmware has
     one global IN ring and one OUT ring; a batch of independent rings is run one ring at a time by moving its state
     into the global the called function uses (oracle/ref_ring.c).  DSP_BUFF_SIZE is the firmware's: 768 frames."""
 
     def __init__(self, channels, frames=None):
-        # RTLD_LAZY: dsp_if.c / main.c also hold functions that call the HAL; the harness never reaches them
-        self.L = C.CDLL(os.path.join(REF_DIR, "libdsp_if_ref.so"), mode=os.RTLD_LAZY)
-        vp, L = C.c_void_p, self.L
-        L.ref_ring_set.argtypes = [C.c_int, vp, vp, C.c_uint8, C.c_uint16, C.c_uint16]
-        L.ref_ring_get.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]
-        L.ref_ring_in_write.argtypes = [vp, C.c_uint16]
-        L.ref_ring_in_read.argtypes = [vp, C.c_uint32]
-        L.ref_ring_out_write.argtypes = [vp, C.c_uint32]
-        L.ref_ring_out_read.argtypes = [vp, C.c_uint16]
-        for fn in ("ref_ring_set", "ref_ring_get", "ref_ring_in_write", "ref_ring_in_read", "ref_ring_out_write",
-                   "ref_ring_out_read", "ref_ring_out_mute"):
-            getattr(L, fn).restype = None
-        self.frames = int(self.L.ref_ring_frames())
+        self.live = ring_ref_available()
+        self._trail_start("ring", channels)
+        if self.live:
+            # RTLD_LAZY: dsp_if.c / main.c also hold functions that call the HAL; the harness never reaches them
+            self.L = C.CDLL(os.path.join(REF_DIR, "libdsp_if_ref.so"), mode=os.RTLD_LAZY)
+            vp, L = C.c_void_p, self.L
+            L.ref_ring_set.argtypes = [C.c_int, vp, vp, C.c_uint8, C.c_uint16, C.c_uint16]
+            L.ref_ring_get.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]
+            L.ref_ring_in_write.argtypes = [vp, C.c_uint16]
+            L.ref_ring_in_read.argtypes = [vp, C.c_uint32]
+            L.ref_ring_out_write.argtypes = [vp, C.c_uint32]
+            L.ref_ring_out_read.argtypes = [vp, C.c_uint16]
+            for fn in ("ref_ring_set", "ref_ring_get", "ref_ring_in_write", "ref_ring_in_read", "ref_ring_out_write",
+                       "ref_ring_out_read", "ref_ring_out_mute"):
+                getattr(L, fn).restype = None
+        self.frames = self._ref_int("frames", (), lambda: self.L.ref_ring_frames())
         assert frames in (None, self.frames), "the firmware's DSP_BUFF_SIZE is %d" % self.frames
         self.channels = channels
         self.s = {"i": np.zeros((channels, self.frames), np.int16), "q": np.zeros((channels, self.frames), np.int16),
                   "buff_enable": np.zeros(channels, np.uint8), "rd_ptr": np.zeros(channels, np.uint16),
                   "wr_ptr": np.zeros(channels, np.uint16)}
+
+    def audio_freq(self):
+        return self._ref_int("audio_freq", (), lambda: self.L.ref_ring_audio_freq())
 
     def _each(self, out, fn):
         s = self.s
@@ -285,31 +513,44 @@ class RefRing:
 
     def in_write(self, pkt):
         pkt = np.ascontiguousarray(pkt, np.int16)
-        self._each(0, lambda c: self.L.ref_ring_in_write(pkt[c].ctypes.data, pkt.shape[1]))
+        self._step("in_write", (pkt,), lambda: self._each(0, lambda c: self.L.ref_ring_in_write(pkt[c].ctypes.data, pkt.shape[1])))
 
     def out_write(self, pkt):
         pkt = np.ascontiguousarray(pkt, np.int16)
-        self._each(1, lambda c: self.L.ref_ring_out_write(pkt[c].ctypes.data, 2 * pkt.shape[1]))
+        self._step("out_write", (pkt,), lambda: self._each(1, lambda c: self.L.ref_ring_out_write(pkt[c].ctypes.data, 2 * pkt.shape[1])))
 
     def in_read(self, size_bytes):
         out = np.zeros((self.channels, size_bytes // 2), np.int16)
-        self._each(0, lambda c: self.L.ref_ring_in_read(out[c].ctypes.data, size_bytes))
-        return out
+
+        def run():
+            self._each(0, lambda c: self.L.ref_ring_in_read(out[c].ctypes.data, size_bytes))
+            return (out,)
+        return self._ref("in_read", (size_bytes,), run, as_digest=True)[0]
 
     def out_read(self, size_words):
         out = np.zeros((self.channels, size_words), np.int16)
-        self._each(1, lambda c: self.L.ref_ring_out_read(out[c].ctypes.data, size_words))
-        return out
+
+        def run():
+            self._each(1, lambda c: self.L.ref_ring_out_read(out[c].ctypes.data, size_words))
+            return (out,)
+        return self._ref("out_read", (size_words,), run, as_digest=True)[0]
 
     def mute(self):
-        self._each(1, lambda c: self.L.ref_ring_out_mute())
+        self._step("mute", (), lambda: self._each(1, lambda c: self.L.ref_ring_out_mute()))
 
     def state(self):
-        return {k: v.copy() for k, v in self.s.items()}
+        keys = sorted(self.s)
+        return dict(zip(keys, self._ref("state", (), lambda: tuple(self.s[k].copy() for k in keys))))
+
+    def state_digest(self):
+        """state_digest(self.state()), without recording the whole state"""
+        return self._ref("state_digest", (), lambda: (state_digest(self.s),), as_digest=True)[0]
 
     def set_state(self, a):
-        for k in self.s:
-            self.s[k][...] = a[k]
+        def run():
+            for k in self.s:
+                self.s[k][...] = a[k]
+        self._step("set_state", ({k: np.asarray(a[k], self.s[k].dtype) for k in self.s},), run)
 
 
 class OracleRing:
@@ -344,6 +585,9 @@ class OracleRing:
     def _np(self, name, shape, dtype):
         ptr = getattr(self.L, "orc_ring_" + name)(self.h)
         return np.ctypeslib.as_array(ptr, shape=shape).view(dtype)
+
+    def state_digest(self):
+        return state_digest(self.state())
 
     def state(self):
         C_, N = self.channels, self.frames
@@ -416,53 +660,68 @@ def synth_audio(first_channel, nch, first_sample, nsamp):
     return np.ascontiguousarray(synth_iq(first_channel, nch, first_sample, nsamp)[:, :, 0])
 
 
-class TxCpuChain:
-    """tx_oracle.c ('orc') or the real-CMSIS composition ref_tx.c ('ref') behind one face."""
+class TxCpuChain(_RefInstance):
+    """tx_oracle.c ('orc') or the real-CMSIS composition ref_tx.c ('ref': live or recorded, ref_call) behind one face."""
 
     def __init__(self, spec, which="orc"):
         self.spec, self.which = spec, which
-        self.L = oracle_lib() if which == "orc" else ref_lib()
+        self.live = which == "orc" or ref_available()
+        self.L = (oracle_lib() if which == "orc" else ref_lib()) if self.live else None
         self.cfg = spec.config()
         self.h = C.c_void_p()
         pre = which + "_tx_"
-        getattr(self.L, pre + "create").argtypes = [C.POINTER(C.c_void_p), C.POINTER(TxConfig)]
-        for n in ("process_f32", "process_q15"):
-            getattr(self.L, pre + n).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
-            getattr(self.L, pre + n).restype = None
-        getattr(self.L, pre + "get_state").argtypes = [C.c_void_p, C.POINTER(TxStateView)]
-        getattr(self.L, pre + "set_mode").argtypes = [C.c_void_p, C.c_uint8]
-        getattr(self.L, pre + "destroy").argtypes = [C.c_void_p]
-        self.rc = getattr(self.L, pre + "create")(C.byref(self.h), C.byref(self.cfg))
+        if self.live:
+            getattr(self.L, pre + "create").argtypes = [C.POINTER(C.c_void_p), C.POINTER(TxConfig)]
+            for n in ("process_f32", "process_q15"):
+                getattr(self.L, pre + n).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+                getattr(self.L, pre + n).restype = None
+            getattr(self.L, pre + "get_state").argtypes = [C.c_void_p, C.POINTER(TxStateView)]
+            getattr(self.L, pre + "set_mode").argtypes = [C.c_void_p, C.c_uint8]
+            getattr(self.L, pre + "destroy").argtypes = [C.c_void_p]
+        create = lambda: getattr(self.L, pre + "create")(C.byref(self.h), C.byref(self.cfg))
+        if which == "ref":
+            self._trail_start(spec_digest("tx", spec))
+            self.rc = self._ref_int("create", (), create)
+        else:
+            self.rc = create()
 
     def ok(self):
-        return self.rc == 0 and bool(self.h)
+        return self.rc == 0 and (bool(self.h) or not self.live)
 
     def set_mode(self, mode):
-        return getattr(self.L, self.which + "_tx_set_mode")(self.h, mode)
+        run = lambda: getattr(self.L, self.which + "_tx_set_mode")(self.h, mode)
+        return self._ref_int("set_mode", (mode,), run) if self.which == "ref" else run()
+
+    def _process(self, name, audio, dtype):
+        c, bs = audio.shape
+        out = np.empty((c, bs * self.spec.interp, 2), dtype)
+
+        def run():
+            getattr(self.L, self.which + "_tx_" + name)(self.h, audio.ctypes.data, out.ctypes.data, bs)
+            return (out,)
+        return (self._ref(name, (audio,), run, as_digest=True) if self.which == "ref" else run())[0]
 
     def process(self, audio):
-        audio = np.ascontiguousarray(audio, np.float32)
-        c, bs = audio.shape
-        out = np.empty((c, bs * self.spec.interp, 2), np.float32)
-        getattr(self.L, self.which + "_tx_process_f32")(self.h, audio.ctypes.data, out.ctypes.data, bs)
-        return out
+        return self._process("process_f32", np.ascontiguousarray(audio, np.float32), np.float32)
 
     def process_q15(self, audio):
-        audio = np.ascontiguousarray(audio, np.int16)
-        c, bs = audio.shape
-        out = np.empty((c, bs * self.spec.interp, 2), np.int16)
-        getattr(self.L, self.which + "_tx_process_q15")(self.h, audio.ctypes.data, out.ctypes.data, bs)
-        return out
+        return self._process("process_q15", np.ascontiguousarray(audio, np.int16), np.int16)
 
     def state(self):
         a = self.spec.state_arrays()
-        v = TxStateView()
-        v.fir_state = fptr(a["fir_state"]) if a["fir_state"].size else None
-        v.interp_state = fptr(a["interp_state"]) if a["interp_state"].size else None
-        v.alc_gain = fptr(a["alc_gain"])
-        v.nco_phase = a["nco_phase"].ctypes.data_as(u32p)
-        getattr(self.L, self.which + "_tx_get_state")(self.h, C.byref(v))
-        return a
+
+        def run():
+            v = TxStateView()
+            v.fir_state = fptr(a["fir_state"]) if a["fir_state"].size else None
+            v.interp_state = fptr(a["interp_state"]) if a["interp_state"].size else None
+            v.alc_gain = fptr(a["alc_gain"])
+            v.nco_phase = a["nco_phase"].ctypes.data_as(u32p)
+            getattr(self.L, self.which + "_tx_get_state")(self.h, C.byref(v))
+            return tuple(a[k] for k in sorted(a))
+        if self.which == "orc":
+            run()
+            return a
+        return dict(zip(sorted(a), self._ref("state", (), run, as_digest=True)))
 
     def __del__(self):
         try:

@@ -1,11 +1,13 @@
-"""GPU: bench.py keeps its contract -- one JSON line with the fields the driver reads, the roofline
-object measured live, the cpu_baseline object, for the f32 and the int16-slot formats.  Small shapes
-(the numbers are not asserted, only their presence and consistency)."""
+"""GPU: bench.py keeps its contract -- one JSON line with the fields the driver reads; with --full the roofline
+object measured live, the cpu_baseline object, for the f32 and the int16-slot formats; a plain run lean, its
+--dump-outputs the audio of its last timed step.  Small shapes (the numbers are not asserted, only their presence and
+consistency)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import rxcommon as rc
@@ -16,7 +18,7 @@ BENCH = os.path.join(rc.ROOT, "bench.py")
 
 def run_bench(*args):
     out = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "4", "--spinup-ms", "0",
-                          "--channels", "1024"] + list(args), check=True, capture_output=True, text=True, timeout=600)
+                          "--channels", "1024", "--full"] + list(args), check=True, capture_output=True, text=True, timeout=600)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
     return json.loads(lines[0])
@@ -111,6 +113,35 @@ def test_bench_q15_slots_cw_shape_and_global_gain():
     assert g["config"]["agc"] == "global" and g["config"]["kernel"].startswith("k_ssb_split16<256,4,63>")
 
 
+def test_a_plain_run_is_lean_and_dumps_the_audio_of_its_last_timed_step(tmp_path):
+    """Without --full the line carries the headline and nothing that takes runs of its own; --dump-outputs writes the audio of the last
+    timed step: the same bits for the same arguments however many calls the clock spin-up took, and what the oracle gives after the
+    same calls (16 behind the reset that follows the spin-up, the warm-up, the timed steps -- the same block each call)."""
+    audio = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        out = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "2", "--spinup-ms", "30" if k else "80", "--channels", "1024",
+                              "--arith", "cmsis", "--dump-outputs", str(d)], check=True, capture_output=True, text=True, timeout=600)
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+        for key in ("streaming_roof", "other_arith_modes", "other_nco_modes", "workloads", "cpu_baseline", "parity", "cfg5_weak_scaling"):
+            assert key not in line, key
+        assert line["roofline"]["launch_ms_median"] is None
+        assert sorted(os.listdir(d)) == ["audio.npy"]
+        audio.append(np.load(d / "audio.npy"))
+    assert audio[0].dtype == np.float32 and audio[0].shape == (1024, 1024)
+    assert rc.bits_equal(audio[0], audio[1])
+    orc = rc.CpuChain(rc.baseline_spec("cfg3", 16, rc.ARITH_CMSIS), "orc")
+    iq = rc.synth_iq(0, 16, 0, 4096)
+    for _ in range(16 + 2 + 3):
+        want = orc.process(iq)
+    assert rc.bits_equal(audio[0][:16], want)
+
+
 def test_pure_c_host_benchmark_agrees_with_the_python_driven_one():
     """selenite-lite_amd/host/bench_rx.c: the north star's "host code stays C" call pattern, measured."""
     exe = os.path.join(rc.PKG_DIR, "host", "bench_rx")
@@ -127,7 +158,7 @@ def test_bench_launches_its_own_ranks_and_shards_the_channels():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["SELENITE_BENCH_SHARE_GPU"] = "1"
     out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dist-backend", "gloo", "--steps", "3", "--warmup", "1",
-                          "--spinup-ms", "0", "--channels", "1024", "--main-only"], capture_output=True, text=True,
+                          "--spinup-ms", "0", "--channels", "1024", "--full", "--main-only"], capture_output=True, text=True,
                          timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -159,7 +190,7 @@ def test_bench_under_the_nccl_backend_with_one_rank_carries_the_dist_block():
     env.update(SELENITE_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29611", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for extra, coll in ((["--n1-ms", "0.5", "--n1-cfg5-ms", "0.25"], 0), (["--global-gain"], 1)):
         out = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "4", "--spinup-ms", "0", "--channels", "1024",
-                              "--main-only"] + extra, capture_output=True, text=True, timeout=900, env=env)
+                              "--full", "--main-only"] + extra, capture_output=True, text=True, timeout=900, env=env)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
         ds = d["dist"]

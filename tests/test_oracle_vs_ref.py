@@ -1,16 +1,16 @@
-"""CPU, build container only: the oracle against the REAL CMSIS-DSP 1.5.3 code compiled from
-/root/reference (oracle/_ref/libcmsis_ref.so), live and on more inputs than the committed
-fixtures hold.  Skipped where the reference library cannot exist (the GPU box)."""
+"""CPU: the oracle against the REAL CMSIS-DSP 1.5.3 code compiled from the reference sources
+(oracle/_ref/libcmsis_ref.so) on more inputs than the chain fixtures hold -- live where that library is built, against
+its recorded answers to the same calls everywhere else (tests/golden/ref_calls.npz, rxcommon.ref_call)."""
 import numpy as np
 import pytest
 
 import rxcommon as rc
-from rxcommon import ARITH_CMSIS as A0, bits_equal, fptr
+from rxcommon import ARITH_CMSIS as A0, bits_equal, fptr, identical
 
 
 def test_sin_table(oracle, ref):
     a = np.ctypeslib.as_array(oracle.orc_sin_table(), (513,))
-    b = np.ctypeslib.as_array(ref.ref_sin_table(), (513,))
+    b = ref.sin_table()
     assert bits_equal(a, b)
 
 
@@ -19,11 +19,10 @@ def test_sin_cos_dense_sweep(oracle, ref):
     x = np.concatenate([np.arange(0, 1 << 24, 257, dtype=np.uint32).astype(np.float32) * np.float32(2 * np.pi / 2 ** 24),
                         (rng.random(20000, dtype=np.float32) - np.float32(0.5)) * np.float32(1000.0),
                         -np.logspace(-9, -5, 200).astype(np.float32)]).astype(np.float32)
-    s, c = np.empty_like(x), np.empty_like(x)
-    ref.ref_sin_cos(fptr(x), fptr(s), fptr(c), x.size)
+    s, c = ref.sin_cos(x)
     so = np.array([oracle.orc_sin_f32(float(v), A0) for v in x], np.float32)
     co = np.array([oracle.orc_cos_f32(float(v), A0) for v in x], np.float32)
-    assert bits_equal(so, s) and bits_equal(co, c)
+    assert identical(so, s) and identical(co, c)
 
 
 @pytest.mark.parametrize("nt,M,blk", [(256, 4, 256), (255, 4, 256), (7, 1, 5), (100, 5, 50), (31, 2, 6), (4, 4, 4)])
@@ -33,9 +32,9 @@ def test_fir_decimate_random(oracle, ref, nt, M, blk):
     sa, sb = np.zeros(nt - 1 + blk, np.float32), np.zeros(nt - 1 + blk, np.float32)
     for _ in range(5):
         x = rng.standard_normal(blk).astype(np.float32)
-        ya, yb = np.empty(blk // M, np.float32), np.empty(blk // M, np.float32)
+        ya = np.empty(blk // M, np.float32)
         oracle.orc_fir_decimate_f32(fptr(c), nt, M, fptr(sa), fptr(x), fptr(ya), blk, A0)
-        ref.ref_fir_decimate(fptr(c), nt, M, fptr(sb), fptr(x), fptr(yb), blk)
+        yb = ref.fir_decimate(c, nt, M, sb, x, blk)
         assert bits_equal(ya, yb) and bits_equal(sa[:nt - 1], sb[:nt - 1])
 
 
@@ -46,9 +45,9 @@ def test_fir_random(oracle, ref, nt, blk):
     sa, sb = np.zeros(nt - 1 + blk, np.float32), np.zeros(nt - 1 + blk, np.float32)
     for _ in range(5):
         x = rng.standard_normal(blk).astype(np.float32)
-        ya, yb = np.empty(blk, np.float32), np.empty(blk, np.float32)
+        ya = np.empty(blk, np.float32)
         oracle.orc_fir_f32(fptr(c), nt, fptr(sa), fptr(x), fptr(ya), blk, A0)
-        ref.ref_fir(fptr(c), nt, fptr(sb), fptr(x), fptr(yb), blk)
+        yb = ref.fir(c, nt, sb, x, blk)
         assert bits_equal(ya, yb) and bits_equal(sa[:nt - 1], sb[:nt - 1])
 
 
@@ -59,15 +58,15 @@ def test_biquad_random(oracle, ref, ns, blk):
     sa, sb = np.zeros(4 * ns, np.float32), np.zeros(4 * ns, np.float32)
     for _ in range(6):
         x = rng.standard_normal(blk).astype(np.float32)
-        ya, yb = np.empty(blk, np.float32), np.empty(blk, np.float32)
+        ya = np.empty(blk, np.float32)
         oracle.orc_biquad_cascade_df1_f32(fptr(c), ns, fptr(sa), fptr(x), fptr(ya), blk, A0)
-        ref.ref_biquad(fptr(c), ns, fptr(sb), fptr(x), fptr(yb), blk)
+        yb = ref.biquad(c, ns, sb, x, blk)
         assert bits_equal(ya, yb) and bits_equal(sa, sb)
 
 
 def test_decimate_init_status_codes(ref):
-    assert ref.ref_fir_decimate_init_status(8, 4, 256) == rc.SUCCESS
-    assert ref.ref_fir_decimate_init_status(8, 4, 255) == rc.LENGTH_ERROR     # arm_fir_decimate_init_f32.c:74-97
+    assert ref.fir_decimate_init_status(8, 4, 256) == rc.SUCCESS
+    assert ref.fir_decimate_init_status(8, 4, 255) == rc.LENGTH_ERROR     # arm_fir_decimate_init_f32.c:74-97
     o = rc.CpuChain(rc.ChainSpec(1, 255, decim=4, nd_taps=8), "orc")
     assert o.rc == rc.LENGTH_ERROR
 
@@ -78,10 +77,10 @@ def test_chain_streaming(name, ref):
     a, b = rc.CpuChain(spec, "orc"), rc.CpuChain(spec, "ref")
     for call in range(4):
         iq = rc.synth_iq(3, 4, call * 768, 768)
-        assert bits_equal(a.process(iq), b.process(iq))
+        assert identical(a.process(iq), b.process(iq))
     sa, sb = a.state(), b.state()
     for k in sa:
-        assert np.array_equal(sa[k].view(np.uint32), sb[k].view(np.uint32)), k
+        assert identical(sa[k], sb[k]), k
 
 
 @pytest.mark.parametrize("mode", [rc.MODE_LSB, rc.MODE_USB, rc.MODE_CW, rc.MODE_CWR, rc.MODE_AM, rc.MODE_FM, rc.MODE_DIG, rc.MODE_PKT])
@@ -92,7 +91,7 @@ def test_chain_all_modes_and_mode_switch(mode, ref):
     for call, m2 in enumerate([mode, rc.MODE_USB, mode]):
         a.set_mode(m2), b.set_mode(m2)
         iq = rc.synth_iq(0, 2, call * 192, 192)
-        assert bits_equal(a.process(iq), b.process(iq))
+        assert identical(a.process(iq), b.process(iq))
 
 
 @pytest.mark.parametrize("blk,M,nd,nh", [(64, 4, 48, 31), (256, 4, 256, 63), (256, 1, 0, 127), (96, 4, 256, 63), (64, 2, 128, 3), (5, 1, 3, 3)])
@@ -107,10 +106,10 @@ def test_fm_chain_against_the_cmsis_composition(blk, M, nd, nh, ref):
     for bs in (blk, 3 * blk, 8 * blk, blk):
         iq = rc.synth_iq(0, 5, pos, bs)
         pos += bs
-        assert bits_equal(a.process(iq), b.process(iq)), bs
+        assert identical(a.process(iq), b.process(iq)), bs
     sa, sb = a.state(), b.state()
     for k in sa:
-        assert np.array_equal(sa[k].view(np.uint32), sb[k].view(np.uint32)), k
+        assert identical(sa[k], sb[k]), k
 
 
 def test_fm_needs_the_delay_lines(ref):
@@ -126,11 +125,11 @@ def test_chain_q15_and_global_gain(ref):
     a, b = rc.CpuChain(spec, "orc"), rc.CpuChain(spec, "ref")
     iq = rc.synth_iq(0, 3, 0, 2048)
     (ya, ea), (yb, eb) = a.process_env(iq), b.process_env(iq)
-    assert bits_equal(ya, yb) and bits_equal(ea, eb)
+    assert identical(ya, yb) and identical(ea, eb)
     spec = rc.baseline_spec("cfg1", 2)
     a, b = rc.CpuChain(spec, "orc"), rc.CpuChain(spec, "ref")
     q = (np.random.default_rng(5).integers(-20000, 20000, (2, 512, 2))).astype(np.int16)
-    assert np.array_equal(a.process_q15(q), b.process_q15(q))
+    assert identical(a.process_q15(q), b.process_q15(q))
 
 
 @pytest.mark.parametrize("shape,block", [((256, 4, 63), 96), ((0, 1, 63), 96), ((128, 2, 63), 96), ((256, 4, 127), 192), ((0, 1, 127), 48)])
@@ -148,9 +147,9 @@ def test_chain_in_the_firmware_block_geometry(shape, block, q15, ref):
         pos += bs
         if q15:
             q = np.clip(np.round(iq * 20000.0), -32768, 32767).astype(np.int16)
-            assert np.array_equal(a.process_q15(q), b.process_q15(q)), bs
+            assert identical(a.process_q15(q), b.process_q15(q)), bs
         else:
-            assert bits_equal(a.process(iq), b.process(iq)), bs
+            assert identical(a.process(iq), b.process(iq)), bs
     sa, sb = a.state(), b.state()
     for k in sa:
-        assert np.array_equal(sa[k].view(np.uint32), sb[k].view(np.uint32)), k
+        assert identical(sa[k], sb[k]), k

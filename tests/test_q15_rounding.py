@@ -1,6 +1,6 @@
 """CPU: the ARM_MATH_ROUNDING variant of arm_float_to_q15 (selenite_rx_config::q15_rounding; arm_float_to_q15.c:90-101) -- the oracle
 against the vectors the reference's own source file produced when built with that define (tests/golden/make_q15_rounding_golden.py),
-and, in the build container, against that build itself on fresh inputs."""
+and against that build itself on further inputs (live where oracle/_ref is built, its recorded answers elsewhere)."""
 import ctypes as C
 import importlib.util
 import os
@@ -66,21 +66,18 @@ def test_chain_vectors(gold, name):
     o.close(); t.close()
 
 
-@pytest.mark.skipif(not rc.ref_available(), reason="oracle/_ref not built (needs /root/reference)")
-def test_oracle_against_the_rounding_build_of_the_reference():
-    R = rc.ref_lib()
+def test_oracle_against_the_rounding_build_of_the_reference(ref):
     rng = np.random.default_rng(31)
     x = np.concatenate([rng.uniform(-1.2, 1.2, 200000), rng.normal(0, 1e-4, 50000),
                         (rng.integers(-33000, 33000, 50000) + rng.choice([0.5, -0.5, 0.499999, 0.500001], 50000)) / 32768.0]).astype(np.float32)
-    want = np.empty(x.size, np.int16)
-    R.arm_float_to_q15_rounding(fptr(x), want.ctypes.data_as(rc.i16p), C.c_uint32(x.size))
-    assert np.array_equal(orc_round(x), want)
+    want = ref.float_to_q15_rounding(x)
+    assert rc.identical(orc_round(x), want)
     spec = rc.ChainSpec(3, block=64, decim=4, nd_taps=48, nh_taps=31, n_biquad=2, mode=rc.MODE_LSB, nco=True, nco_step_all=0x01234567,
                         bp_f0=0.05, bp_q=3.0, q15_rounding=True)
     o, r = rc.CpuChain(spec, "orc"), rc.CpuChain(spec, "ref")
     for call in range(3):
         q = _gen().case_input(3, call, 640)
-        assert np.array_equal(o.process_q15(q), r.process_q15(q))
+        assert rc.identical(o.process_q15(q), r.process_q15(q))
     o.close(); r.close()
 
 

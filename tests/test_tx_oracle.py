@@ -1,12 +1,13 @@
-"""CPU: the TX oracle (oracle/tx_oracle.c) against the real CMSIS-DSP 1.5.3 code -- live in the build
-container (oracle/_ref, skipped elsewhere) and against the committed fixtures everywhere."""
+"""CPU: the TX oracle (oracle/tx_oracle.c) against the real CMSIS-DSP 1.5.3 code -- live where oracle/_ref is
+built, against its recorded answers to the same calls elsewhere (tests/golden/ref_calls.npz) -- and against the
+committed fixtures everywhere."""
 import os
 
 import numpy as np
 import pytest
 
 import rxcommon as rc
-from rxcommon import ARITH_CMSIS as A0, bits_equal, fptr
+from rxcommon import ARITH_CMSIS as A0, bits_equal, fptr, identical
 from golden.make_tx_golden import TX_CASES, prim_interp_cases
 
 GOLD = os.path.join(rc.ROOT, "tests", "golden")
@@ -47,15 +48,14 @@ def test_interpolator_random_vs_real_cmsis(oracle, ref, nt, L, blk):
     sa, sb = np.zeros(nt // L - 1 + blk, np.float32), np.zeros(nt // L - 1 + blk, np.float32)
     for _ in range(5):
         x = rng.standard_normal(blk).astype(np.float32)
-        yb = np.empty(blk * L, np.float32)
-        ref.ref_fir_interpolate(fptr(c), nt, L, fptr(sb), fptr(x), fptr(yb), blk)
+        yb = ref.fir_interpolate(c, nt, L, sb, x, blk)
         assert bits_equal(orc_interp(oracle, c, nt, L, sa, x), yb)
         assert bits_equal(sa[:nt // L - 1], sb[:nt // L - 1])
 
 
 def test_interpolator_init_length_error_matches_cmsis(ref):
-    assert ref.ref_fir_interpolate_init_status(256, 4, 64) == 0
-    assert ref.ref_fir_interpolate_init_status(255, 4, 64) == rc.LENGTH_ERROR       # arm_fir_interpolate_init_f32.c:91-96
+    assert ref.fir_interpolate_init_status(256, 4, 64) == 0
+    assert ref.fir_interpolate_init_status(255, 4, 64) == rc.LENGTH_ERROR       # arm_fir_interpolate_init_f32.c:91-96
     bad = rc.TxSpec(2, ni_taps=256, interp=4)
     bad.ni_taps = 255
     assert rc.TxCpuChain(bad, "orc").rc == rc.LENGTH_ERROR
@@ -87,10 +87,10 @@ def test_tx_chain_all_modes_vs_real_cmsis(ref, mode):
     assert o.ok() and r.ok()
     for k in range(3):
         a = rc.synth_audio(5, 3, k * 96, 96)
-        assert bits_equal(o.process(a), r.process(a))
+        assert identical(o.process(a), r.process(a))
     so, sr_ = o.state(), r.state()
     for key in so:
-        assert np.array_equal(so[key].view(np.uint32), sr_[key].view(np.uint32)), key
+        assert identical(so[key], sr_[key]), key
 
 
 def test_tx_then_rx_loopback_recovers_the_audio_band():

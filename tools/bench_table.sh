@@ -1,11 +1,11 @@
 #!/bin/bash
-# tools/bench_table.sh <outfile> -- bench.py --main-only for every workload / option of interest on ONE box:
+# tools/bench_table.sh <outfile> -- bench.py --full --main-only for every workload / option of interest on ONE box:
 # "<args> | Msamples/s  ms per launch  roofline.frac  kernel  [nco path]"
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$1
 : > $OUT
 run() {
-  python3 $R/bench.py --main-only "$@" 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --main-only "$@" 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('%-34s | %10.1f  %.4f  %.4f  %s  [%s]' % ('$*' or '(default)', d['value'], d['roofline']['launch_ms_hip_events'], d['roofline']['frac'], d['config']['kernel'], d['config']['nco']))" >> $OUT

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for lib in $R/selenite-lite_amd/libselenite_rx.so $R/selenite-lite_amd/variants/lib_*.so; do
   n=$(basename $lib .so)
   SELENITE_RX_LIB=$lib rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_WAVES \
-      --output-format csv -d $O/$n -o c -- python3 $R/bench.py --main-only --spinup-ms 0 --steps 2 --warmup 1 "$@" > /dev/null 2> $O/$n.err
+      --output-format csv -d $O/$n -o c -- python3 $R/bench.py --full --main-only --spinup-ms 0 --steps 2 --warmup 1 "$@" > /dev/null 2> $O/$n.err
 done
 python3 - "$O" <<'PY'
 import csv, glob, os, sys, collections
