@@ -28,6 +28,7 @@
  *   -> arm_fir_f32 (delay taps) on I, arm_fir_f32 (Hilbert taps) on Q
  *   -> arm_sub_f32 / arm_add_f32 (USB / LSB)   [AM: arm_cmplx_mag_f32]
  *   -> arm_biquad_cascade_df1_f32 (CW narrow filter)
+ *   -> [optional: arm_lms_norm_f32 noise reduction / automatic notch, selenite_rx_set_nr]
  *   -> arm_abs_f32 + arm_max_f32 -> gain law -> arm_scale_f32 (AGC)
  */
 #ifndef SELENITE_RX_H
@@ -159,6 +160,43 @@ typedef struct selenite_rx_state_view {
     uint32_t *nco_phase;
 } selenite_rx_state_view;
 
+/* ---- NLMS noise reduction / automatic notch (step 4b of DESIGN.md section 2, between the CW filter and the AGC) -------------
+ * Per channel, on the un-scaled audio x of the demodulator (every mode), at the audio rate:
+ *   u[n] = x[n - delay]                                   decorrelation delay line (zeros after selenite_rx_set_nr)
+ *   arm_lms_norm_f32(S, pSrc = u, pRef = x, pOut = y, pErr = e, n)   (FilteringFunctions/arm_lms_norm_f32.c:161-348, the
+ *                                                         ARM_MATH_DSP branch the firmware's -DARM_MATH_CM4 selects)
+ *   SELENITE_RX_NR_DENOISE passes y (what the input predicts from `delay` samples back: tones, voiced speech; broadband noise falls),
+ *   SELENITE_RX_NR_NOTCH   passes e = x - y (the predictable part removed: carriers, heterodynes);
+ * the AGC then runs on the stage's output.  The stage keeps the reference's rounding in every arith mode (products then sums in
+ * tap order, energy -= x0*x0; energy += in*in, a correctly rounded division, no contraction): given its input it is bit-exact
+ * against arm_lms_norm_f32.  Non-finite stage output raises SELENITE_RX_NANINF like any other. */
+#define SELENITE_RX_NR_OFF     0
+#define SELENITE_RX_NR_DENOISE 1
+#define SELENITE_RX_NR_NOTCH   2
+
+typedef struct selenite_rx_nr_config {
+    uint32_t struct_size;     /* = sizeof(selenite_rx_nr_config) (this struct's own growth path, as selenite_rx_config's) */
+    uint32_t kind;            /* SELENITE_RX_NR_* */
+    uint32_t num_taps;        /* arm_lms_norm_instance_f32.numTaps: 8, 16, 32 or 64 */
+    uint32_t delay;           /* decorrelation delay D in audio samples, 1 .. 64 */
+    float    mu;              /* step size, finite, 0 < mu < 2 */
+    const float *coeffs_init; /* [num_taps] initial weights in pCoeffs order (shared by every channel), or NULL = zeros; copied */
+} selenite_rx_nr_config;
+
+/* Host-side view of the stage's per-channel state; any pointer may be NULL (skipped).  N = num_taps, D = delay:
+ *   coeffs [channels][N]      pCoeffs
+ *   window [channels][N-1]    the last N-1 samples of u, oldest first (arm_lms_norm_f32.c:315-346 copy-back order)
+ *   delay  [channels][D]      the last D samples of x, oldest first
+ *   energy [channels]         arm_lms_norm_instance_f32.energy
+ *   x0     [channels]         arm_lms_norm_instance_f32.x0 */
+typedef struct selenite_rx_nr_state_view {
+    float *coeffs;
+    float *window;
+    float *delay;
+    float *energy;
+    float *x0;
+} selenite_rx_nr_state_view;
+
 typedef struct selenite_rx_instance selenite_rx_instance;  /* opaque; state lives in HBM */
 
 /* ---- instance life cycle ------------------------------------------------------------- */
@@ -285,7 +323,18 @@ int  selenite_rx_sync(selenite_rx_instance *S);
 
 int  selenite_rx_get_state(selenite_rx_instance *S, const selenite_rx_state_view *dst);
 int  selenite_rx_set_state(selenite_rx_instance *S, const selenite_rx_state_view *src);
-int  selenite_rx_reset(selenite_rx_instance *S);      /* state back to the post-init values */
+int  selenite_rx_reset(selenite_rx_instance *S);      /* state back to the post-init values (an NLMS stage: to its post-set_nr values) */
+
+/* ---- NLMS noise reduction / automatic notch --------------------------------------------- */
+
+/* Mirrors arm_lms_norm_init_f32 (FilteringFunctions/arm_lms_norm_init_f32.c:60-89) for every channel: weights = coeffs_init (or 0),
+ * window, delay line, energy and x0 = 0.  nr == NULL or kind == SELENITE_RX_NR_OFF removes the stage.  A field out of range:
+ * SELENITE_RX_ARGUMENT_ERROR, and the instance is left as it was.  selenite_rx_set_mode leaves the stage's state alone; every
+ * process entry point (f32 and int16 slots, device and host pointers, the timing calls, global phase 1) runs it. */
+int  selenite_rx_set_nr(selenite_rx_instance *S, const selenite_rx_nr_config *nr);
+/* The stage's state (layouts: selenite_rx_nr_state_view).  SELENITE_RX_ARGUMENT_ERROR while the stage is off. */
+int  selenite_rx_get_nr_state(selenite_rx_instance *S, const selenite_rx_nr_state_view *dst);
+int  selenite_rx_set_nr_state(selenite_rx_instance *S, const selenite_rx_nr_state_view *src);
 
 void *selenite_rx_device_alloc(size_t bytes);          /* hipMalloc; NULL on failure */
 void  selenite_rx_device_free(void *dptr);

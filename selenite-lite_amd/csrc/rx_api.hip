@@ -114,7 +114,8 @@ static void free_device(selenite_rx_instance *S)
 {
     void *ptrs[] = { S->d_flags, S->d_guard_ch, S->d_rerun_flag, S->d_rerun_list, S->d_hist_ext, S->d_conv_in, S->d_dec_c, S->d_hilb_c, S->d_delay_c, S->d_biq_c, S->d_sintab, S->d_step, S->d_phase,
                      S->d_dec_state, S->d_fir_state, S->d_biq_state, S->d_gain, S->d_scratch, S->d_env, S->d_env_part,
-                     S->d_io_in, S->d_io_out, S->d_lo, S->pipe.d_in[0], S->pipe.d_in[1], S->pipe.d_out[0], S->pipe.d_out[1] };
+                     S->d_io_in, S->d_io_out, S->d_lo, S->pipe.d_in[0], S->pipe.d_in[1], S->pipe.d_out[0], S->pipe.d_out[1],
+                     S->d_nr_coeffs, S->d_nr_window, S->d_nr_delay, S->d_nr_energy, S->d_nr_x0 };
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (S->h_rerun_seen) (void)hipHostFree(S->h_rerun_seen);
@@ -130,6 +131,22 @@ static void free_device(selenite_rx_instance *S)
     if (S->pipe.d2h) (void)hipStreamDestroy(S->pipe.d2h);
     free_fused(S->plan);
     if (S->own_stream) (void)hipStreamDestroy(S->own_stream);
+}
+
+// the NLMS stage's state as arm_lms_norm_init_f32 leaves it (arm_lms_norm_init_f32.c:69-86): weights = the initial ones, the rest 0
+static int nr_init_state(selenite_rx_instance *S)
+{
+    if (S->nr_kind == SELENITE_RX_NR_OFF) return SELENITE_RX_SUCCESS;
+    const size_t C = S->cfg.channels, N = S->nr_taps, D = S->nr_delay;
+    std::vector<float> w(C * N);
+    for (size_t c = 0; c < C; ++c) std::memcpy(&w[c * N], S->h_nr_init.data(), N * sizeof(float));
+    HIPCHK(S, hipMemcpyAsync(S->d_nr_coeffs, w.data(), C * N * sizeof(float), hipMemcpyHostToDevice, S->stream));
+    HIPCHK(S, hipMemsetAsync(S->d_nr_window, 0, C * (N - 1) * sizeof(float), S->stream));
+    HIPCHK(S, hipMemsetAsync(S->d_nr_delay, 0, C * D * sizeof(float), S->stream));
+    HIPCHK(S, hipMemsetAsync(S->d_nr_energy, 0, C * sizeof(float), S->stream));
+    HIPCHK(S, hipMemsetAsync(S->d_nr_x0, 0, C * sizeof(float), S->stream));
+    HIPCHK(S, hipStreamSynchronize(S->stream));      // (w is a host temporary)
+    return SELENITE_RX_SUCCESS;
 }
 
 static int reset_state(selenite_rx_instance *S)
@@ -151,7 +168,7 @@ static int reset_state(selenite_rx_instance *S)
     HIPCHK(S, hipStreamSynchronize(S->stream));
     S->phase_uniform = true;
     S->phase_host = 0;
-    return SELENITE_RX_SUCCESS;
+    return nr_init_state(S);
 }
 
 // the kernels' flag word (non-finite audio: ARM_MATH_NANINF), read after the stream has drained; latches the status
@@ -541,6 +558,100 @@ extern "C" int selenite_rx_reset(selenite_rx_instance *S)
     return reset_state(S);
 }
 
+// ---- NLMS noise reduction / automatic notch (rx_nlms.hip) ----
+static void nr_release(selenite_rx_instance *S)
+{
+    float **bufs[] = { &S->d_nr_coeffs, &S->d_nr_window, &S->d_nr_delay, &S->d_nr_energy, &S->d_nr_x0 };
+    for (float **b : bufs) {
+        if (*b) (void)hipFree(*b);
+        *b = nullptr;
+    }
+    S->nr_kind = SELENITE_RX_NR_OFF;
+    S->nr_taps = S->nr_delay = 0;
+    S->nr_mu = 0.0f;
+    S->h_nr_init.clear();
+}
+
+extern "C" int selenite_rx_set_nr(selenite_rx_instance *S, const selenite_rx_nr_config *nr)
+{
+    if (!S) return fail(nullptr, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_set_nr: S is NULL");
+    // everything is validated before anything changes: a refused call leaves the instance as it was
+    if (nr && nr->struct_size != sizeof(selenite_rx_nr_config)) {
+        g_last_error = "selenite_rx_set_nr: struct_size is not sizeof(selenite_rx_nr_config)";
+        return SELENITE_RX_ARGUMENT_ERROR;
+    }
+    if (nr && nr->kind != SELENITE_RX_NR_OFF) {
+        const uint32_t N = nr->num_taps;
+        const char *bad = nullptr;
+        if (nr->kind != SELENITE_RX_NR_DENOISE && nr->kind != SELENITE_RX_NR_NOTCH) bad = "kind is not a SELENITE_RX_NR_* value";
+        else if (N != 8 && N != 16 && N != 32 && N != 64) bad = "num_taps is not 8, 16, 32 or 64";
+        else if (nr->delay < 1 || nr->delay > 64) bad = "delay is not 1 .. 64";
+        else if (!(nr->mu > 0.0f && nr->mu < 2.0f)) bad = "mu is not finite in (0, 2)";
+        else if (nr->coeffs_init)
+            for (uint32_t k = 0; k < N && !bad; ++k)
+                if (!std::isfinite(nr->coeffs_init[k])) bad = "coeffs_init holds a non-finite weight";
+        if (bad) {
+            g_last_error = std::string("selenite_rx_set_nr: ") + bad;
+            return SELENITE_RX_ARGUMENT_ERROR;
+        }
+    }
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    nr_release(S);
+    if (!nr || nr->kind == SELENITE_RX_NR_OFF) return SELENITE_RX_SUCCESS;
+    const size_t C = S->cfg.channels, N = nr->num_taps, D = nr->delay;
+    S->h_nr_init.assign(N, 0.0f);
+    if (nr->coeffs_init) std::memcpy(S->h_nr_init.data(), nr->coeffs_init, N * sizeof(float));
+    hipError_t e = hipSuccess;
+    if (e == hipSuccess) e = hipMalloc((void **)&S->d_nr_coeffs, C * N * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&S->d_nr_window, C * (N - 1) * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&S->d_nr_delay, C * D * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&S->d_nr_energy, C * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&S->d_nr_x0, C * sizeof(float));
+    if (e != hipSuccess) {
+        nr_release(S);
+        return fail(S, SELENITE_RX_DEVICE_ERROR, std::string("selenite_rx_set_nr: hipMalloc: ") + hipGetErrorString(e));
+    }
+    S->nr_kind = nr->kind; S->nr_taps = (uint32_t)N; S->nr_delay = (uint32_t)D; S->nr_mu = nr->mu;
+    return nr_init_state(S);
+}
+
+// the five arrays of selenite_rx_nr_state_view, device side, with their sizes
+static void nr_arrays(selenite_rx_instance *S, const selenite_rx_nr_state_view *v, float *(&dev)[5], float *(&host)[5], size_t (&n)[5])
+{
+    const size_t C = S->cfg.channels;
+    float *d[5] = { S->d_nr_coeffs, S->d_nr_window, S->d_nr_delay, S->d_nr_energy, S->d_nr_x0 };
+    float *h[5] = { v->coeffs, v->window, v->delay, v->energy, v->x0 };
+    const size_t m[5] = { C * S->nr_taps, C * (S->nr_taps - 1), C * S->nr_delay, C, C };
+    for (int i = 0; i < 5; ++i) { dev[i] = d[i]; host[i] = h[i]; n[i] = m[i]; }
+}
+
+extern "C" int selenite_rx_get_nr_state(selenite_rx_instance *S, const selenite_rx_nr_state_view *v)
+{
+    if (!S || !v || S->nr_kind == SELENITE_RX_NR_OFF) return SELENITE_RX_ARGUMENT_ERROR;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    float *dev[5], *host[5];
+    size_t n[5];
+    nr_arrays(S, v, dev, host, n);
+    for (int i = 0; i < 5; ++i)
+        if (host[i] && n[i]) HIPCHK(S, hipMemcpy(host[i], dev[i], n[i] * sizeof(float), hipMemcpyDeviceToHost));
+    return SELENITE_RX_SUCCESS;
+}
+
+extern "C" int selenite_rx_set_nr_state(selenite_rx_instance *S, const selenite_rx_nr_state_view *v)
+{
+    if (!S || !v || S->nr_kind == SELENITE_RX_NR_OFF) return SELENITE_RX_ARGUMENT_ERROR;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    float *dev[5], *host[5];
+    size_t n[5];
+    nr_arrays(S, v, dev, host, n);
+    for (int i = 0; i < 5; ++i)
+        if (host[i] && n[i]) HIPCHK(S, hipMemcpy(dev[i], host[i], n[i] * sizeof(float), hipMemcpyHostToDevice));
+    return SELENITE_RX_SUCCESS;
+}
+
 // ------------------------------------------------------------------------------------------
 static RxParams make_params(selenite_rx_instance *S, uint32_t block_size)
 {
@@ -581,6 +692,22 @@ static RxParams make_params(selenite_rx_instance *S, uint32_t block_size)
     return p;
 }
 
+// the NLMS stage's view of a launch: the channels (and channel range) and the audio geometry of `p`
+static NrParams make_nr_params(const selenite_rx_instance *S, const RxParams &p)
+{
+    NrParams q{};
+    q.channels = p.channels; q.nout = p.nout; q.stride = p.out_stride;
+    q.delay = S->nr_delay; q.notch = S->nr_kind == SELENITE_RX_NR_NOTCH ? 1u : 0u; q.mu = S->nr_mu;
+    q.coeffs = S->d_nr_coeffs; q.window = S->d_nr_window; q.delay_line = S->d_nr_delay; q.energy = S->d_nr_energy; q.x0 = S->d_nr_x0;
+    q.flags = p.flags;
+    if (S->sub_count) {                                     // a channel range of the instance (make_params): the stage's arrays move with it
+        const size_t c0 = S->sub_first;
+        q.coeffs += c0 * S->nr_taps; q.window += c0 * (S->nr_taps - 1); q.delay_line += c0 * S->nr_delay;
+        q.energy += c0; q.x0 += c0;
+    }
+    return q;
+}
+
 static int ensure(selenite_rx_instance *S, void **buf, size_t *cap, size_t need)
 {
     if (*cap >= need) return SELENITE_RX_SUCCESS;
@@ -617,6 +744,7 @@ static int run_part(selenite_rx_instance *S, const void *src, bool src_q15, void
     const int garith = arith == SELENITE_ARITH_AUTO ? SELENITE_ARITH_CMSIS : arith;      // the generic kernels: AUTO is bit-exact there
     const bool global = g.agc_enable && g.agc_global;
     const bool cw = mode_is_cw(g.mode) && g.n_biquad;
+    const bool nr = phase != kPhase2 && S->nr_kind != SELENITE_RX_NR_OFF;      // NLMS stage in front of the AGC (rx_nlms.hip)
     hipStream_t st = S->stream;
 
     // host copy of the common NCO phase (valid while every channel shares step and phase)
@@ -630,11 +758,14 @@ static int run_part(selenite_rx_instance *S, const void *src, bool src_q15, void
     // (the fused kernels convert in and out symmetrically, and a global gain needs f32 audio between its two phases: int16 slots with
     // a global gain get their input converted once, up front -- arm_q15_to_float over the whole buffer, the very operation the fused
     // int16 load performs -- and run as an f32-input call whose gain pass stores int16; round 2 left them to the generic kernels)
+    // (the NLMS stage the same way: the fused kernel leaves un-scaled f32 audio, the stage runs in place on it, the AGC pass stores)
     const bool fusable = phase != kPhase2 && !S->force_generic;
     const bool ssb_fused = fusable && S->plan.kind != 0;
     const bool cw_fused = fusable && cw_fused_ok(g, block_size) && cw_strides_ok(p.in_stride, p.out_stride);    // (wider strides: the generic kernels)
-    if (global && src_q15 && (ssb_fused || cw_fused)) {
-        const size_t nval = (size_t)p.channels * p.in_stride * 2;            // int16 values of the call (block_size % 4 == 0 for every fused shape)
+    if ((global || nr) && src_q15 && (ssb_fused || cw_fused)) {
+        // int16 values of the call (block_size % 4 == 0 for every fused shape), up to the end of the last channel's block_size samples: the
+        // second part of a fused_tail_split call starts inside the rows (= p.channels * p.in_stride * 2 when the call is not split)
+        const size_t nval = ((size_t)(p.channels - 1) * p.in_stride + block_size) * 2;
         if (nval % 8 == 0) {
             int rc = ensure(S, (void **)&S->d_conv_in, &S->conv_in_bytes, nval * sizeof(float));
             if (rc) return rc;
@@ -644,7 +775,7 @@ static int run_part(selenite_rx_instance *S, const void *src, bool src_q15, void
         }
     }
     float *audio = (float *)dst;      // un-scaled audio: dst itself when dst is f32, else scratch
-    if (dst_q15 && (global || !(ssb_fused || cw_fused))) {
+    if (dst_q15 && (global || nr || !(ssb_fused || cw_fused))) {
         const size_t need = (size_t)g.channels * p.out_stride * sizeof(float);
         int rc = ensure(S, (void **)&S->d_scratch, &S->scratch_bytes, need);
         if (rc) return rc;
@@ -701,12 +832,12 @@ static int run_part(selenite_rx_instance *S, const void *src, bool src_q15, void
         }
         void *fdst = dst;
         bool fq15 = dst_q15;
-        if (global) {
+        if (global || nr) {
             pf.agc = 0; fdst = audio; fq15 = false;
             pf.out_cached = 1;                            // phase 2 (and, without block maxima from the kernel, the envelope fold) reads this audio back
             // k_ssb_split16 (16-lane DSP blocks, whole passes) leaves the block maxima of every channel behind: the
             // envelope reduction below then folds channels x blocks floats instead of reading the audio again
-            if (ssb_fused && (arith == SELENITE_ARITH_SPLIT16 || arith == SELENITE_ARITH_AUTO) && S->plan.d_btab16 && g.nd_taps && g.decim == 4 && (g.block / g.decim) / 4 == 16 &&
+            if (!nr && ssb_fused && (arith == SELENITE_ARITH_SPLIT16 || arith == SELENITE_ARITH_AUTO) && S->plan.d_btab16 && g.nd_taps && g.decim == 4 && (g.block / g.decim) / 4 == 16 &&
                 (block_size / g.decim) % 256 == 0 && g.nco_enable && g.mode != SELENITE_MODE_AM && g.mode != SELENITE_MODE_FM) {   // the launches with the DPP block reductions (decimation by 4, 64-sample audio blocks)
                 const size_t need = sizeof(float) * env_fold_scratch_floats(p.channels, block_size / g.block);
                 int rc = ensure(S, (void **)&S->d_env_part, &S->env_part_cap, need);
@@ -718,7 +849,7 @@ static int run_part(selenite_rx_instance *S, const void *src, bool src_q15, void
         if (ssb_fused) HIPCHK(S, launch_fused(S->plan, pf, arith, src, src_q15, fdst, fq15, S->delay_index, st));
         else HIPCHK(S, launch_cw_fused(pf, src, src_q15, fdst, fq15, st));
         commit_phase();
-        if (!global) return SELENITE_RX_SUCCESS;
+        if (!global && !nr) return SELENITE_RX_SUCCESS;
     }
 
     // generic path: front -> [biquad] -> AGC / convert
@@ -727,6 +858,8 @@ static int run_part(selenite_rx_instance *S, const void *src, bool src_q15, void
         commit_phase();
         if (cw) HIPCHK(S, launch_biquad_generic(p, garith, audio, st));
     }
+    // step 4b: NLMS in place on the un-scaled audio (phase 1 of a global gain: before the envelope)
+    if (nr) HIPCHK(S, launch_nlms(make_nr_params(S, p), S->nr_taps, audio, st));
     if (global) {
         float *env = ext_env;
         if (!env) {

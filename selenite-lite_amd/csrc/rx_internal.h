@@ -135,6 +135,23 @@ hipError_t launch_env_fold(float *part, float *env, uint32_t rows, uint32_t nblk
 hipError_t launch_agc_apply_global(const RxParams &p, int arith, const float *audio, const float *env,
                                    void *dst, bool dst_q15, hipStream_t st);
 
+// ---- NLMS noise reduction / automatic notch (rx_nlms.hip): in place on un-scaled f32 audio, between the demodulator and the AGC ----
+struct NrParams {
+    uint32_t channels;     // channels of this launch (a sub-range on the host-pointer path: the arrays below are offset to it)
+    uint32_t nout;         // audio samples per channel in this call
+    uint32_t stride;       // audio samples between consecutive channels (RxParams::out_stride)
+    uint32_t delay;        // D
+    uint32_t notch;        // 1: output e = x - y (SELENITE_RX_NR_NOTCH), 0: y (SELENITE_RX_NR_DENOISE)
+    float mu;
+    float *coeffs;         // [C][N]
+    float *window;         // [C][N-1] oldest first
+    float *delay_line;     // [C][D] oldest first
+    float *energy;         // [C]
+    float *x0;             // [C]
+    uint32_t *flags;       // RxParams::flags (kFlagNanInf)
+};
+hipError_t launch_nlms(const NrParams &q, uint32_t num_taps, float *audio, hipStream_t st);
+
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
     int kind = 0;                 // 0 = none
@@ -249,6 +266,11 @@ struct selenite_rx_instance {
     int no_shared_lo = 0;              // SELENITE_RX_NO_SHARED_LO=1: always compute the LO per channel
     int no_periodic_lo = 0;            // SELENITE_RX_NO_PERIODIC_LO=1: never keep a periodic shared LO in registers
     int force_generic = 0;             // SELENITE_RX_FORCE_GENERIC=1 (tests cross-check both paths)
+    // NLMS stage (selenite_rx_set_nr): kind SELENITE_RX_NR_OFF = no stage, no buffers
+    uint32_t nr_kind = SELENITE_RX_NR_OFF, nr_taps = 0, nr_delay = 0;
+    float nr_mu = 0.0f;
+    std::vector<float> h_nr_init;      // [nr_taps] the weights set_nr / reset start from
+    float *d_nr_coeffs = nullptr, *d_nr_window = nullptr, *d_nr_delay = nullptr, *d_nr_energy = nullptr, *d_nr_x0 = nullptr;
     int status = SELENITE_RX_SUCCESS;
     std::string err;
 };

@@ -21,6 +21,7 @@ ARITH_CMSIS, ARITH_FMA, ARITH_SPLIT16, ARITH_AUTO = 0, 1, 2, 3
 ABI_VERSION, CONFIG_SIZE_V1, TX_CONFIG_SIZE_V1 = 2, 112, 96      # include/selenite_rx.h, selenite_tx.h
 OPT_FORCE_GENERIC, OPT_NO_SHARED_LO, OPT_NO_PERIODIC_LO, OPT_RERUN_GRID, OPT_TX_FORCE_GENERIC, OPT_CW_GRID = 0, 1, 2, 3, 4, 5      # selenite_rx_set_plan_option
 SUCCESS, ARGUMENT_ERROR, LENGTH_ERROR, NANINF, DEVICE_ERROR = 0, -1, -2, -4, -7
+NR_OFF, NR_DENOISE, NR_NOTCH = 0, 1, 2                         # selenite_rx_set_nr: the NLMS stage's kind
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -50,6 +51,17 @@ class StateView(C.Structure):
                 ("agc_gain", f32p), ("nco_phase", u32p)]
 
 
+class NrConfig(C.Structure):
+    """struct selenite_rx_nr_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("num_taps", C.c_uint32), ("delay", C.c_uint32),
+                ("mu", C.c_float), ("coeffs_init", f32p)]
+
+
+class NrStateView(C.Structure):
+    """struct selenite_rx_nr_state_view."""
+    _fields_ = [("coeffs", f32p), ("window", f32p), ("delay", f32p), ("energy", f32p), ("x0", f32p)]
+
+
 # every symbol include/selenite_rx.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "selenite_rx_init", "selenite_rx_free", "selenite_rx_set_mode", "selenite_rx_status",
@@ -67,6 +79,7 @@ ABI_SYMBOLS = [
     "selenite_rx_host_alloc", "selenite_rx_host_free", "selenite_rx_host_register", "selenite_rx_host_unregister",
     "selenite_rx_time_process_each_device", "selenite_rx_time_streaming_roof_device", "selenite_rx_time_pattern_roof_device", "selenite_rx_device_pci_bus_id", "selenite_rx_set_plan_option", "selenite_rx_get_plan_option",
     "selenite_rx_set_guard_ratio", "selenite_rx_guard_stats", "selenite_rx_guard_channels", "selenite_rx_auto_words", "selenite_rx_guard_handover", "selenite_rx_set_handover_repair", "selenite_rx_set_auto_launches", "selenite_rx_auto_launches_last", "selenite_rx_guard_clear",
+    "selenite_rx_set_nr", "selenite_rx_get_nr_state", "selenite_rx_set_nr_state",
 ]
 
 class TxConfig(C.Structure):
@@ -183,6 +196,10 @@ def lib():
         L.selenite_rx_set_handover_repair.argtypes = [vp, C.c_int]
         L.selenite_rx_set_auto_launches.argtypes = [vp, C.c_int]
         L.selenite_rx_auto_launches_last.argtypes = [vp]
+        if hasattr(L, "selenite_rx_set_nr"):                # (an older build named by SELENITE_RX_LIB lacks the NLMS stage)
+            L.selenite_rx_set_nr.argtypes = [vp, C.POINTER(NrConfig)]
+            L.selenite_rx_get_nr_state.argtypes = [vp, C.POINTER(NrStateView)]
+            L.selenite_rx_set_nr_state.argtypes = [vp, C.POINTER(NrStateView)]
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -527,6 +544,53 @@ class Rx:
         rc = self.L.selenite_rx_set_state(self.h, C.byref(v))
         if rc:
             raise RxError(rc, self.error())
+
+    # -- NLMS noise reduction / automatic notch (selenite_rx_set_nr) --------------------------
+    def set_nr(self, kind, num_taps=32, delay=16, mu=0.05, coeffs_init=None):
+        """(Re)initialise the NLMS stage of every channel (NR_DENOISE / NR_NOTCH), or remove it (NR_OFF).  Raises RxError on a bad field;
+        the instance is then left as it was."""
+        g = NrConfig()
+        g.struct_size = C.sizeof(NrConfig)
+        g.kind, g.num_taps, g.delay, g.mu = int(kind), int(num_taps), int(delay), float(mu)
+        w = None
+        if coeffs_init is not None:
+            w = np.ascontiguousarray(coeffs_init, np.float32)
+            g.coeffs_init = _fp(w)
+        # (a refused field leaves the old stage in place, but a failed allocation leaves NO stage: forget it until the call succeeds, and
+        # on a refusal ask the library whether the old one is still there)
+        old, self._nr = getattr(self, "_nr", None), None
+        rc = self.L.selenite_rx_set_nr(self.h, C.byref(g))
+        if rc == ARGUMENT_ERROR:
+            self._nr = old
+        if rc:
+            raise RxError(rc, self.L.selenite_rx_error_string(None).decode() if rc == ARGUMENT_ERROR else self.error())
+        self._nr = (int(num_taps), int(delay)) if kind != NR_OFF else None
+
+    def _nr_arrays(self):
+        if getattr(self, "_nr", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the NLMS stage is off")
+        n, d = self._nr
+        c = self.cfg.channels
+        return dict(coeffs=np.zeros((c, n), np.float32), window=np.zeros((c, n - 1), np.float32),
+                    delay=np.zeros((c, d), np.float32), energy=np.zeros(c, np.float32), x0=np.zeros(c, np.float32))
+
+    def nr_state(self):
+        a = self._nr_arrays()
+        v = NrStateView(*[_fp(a[k]) for k in ("coeffs", "window", "delay", "energy", "x0")])
+        rc = self.L.selenite_rx_get_nr_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_nr_state")
+        return a
+
+    def set_nr_state(self, d):
+        shapes = self._nr_arrays()
+        a = {k: np.ascontiguousarray(d[k], np.float32) for k in d}
+        for k in a:
+            assert a[k].shape == shapes[k].shape, (k, a[k].shape)
+        v = NrStateView(*[_fp(a[k]) if k in a else None for k in ("coeffs", "window", "delay", "energy", "x0")])
+        rc = self.L.selenite_rx_set_nr_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_set_nr_state")
 
     def close(self):
         if self.h:
