@@ -44,10 +44,20 @@ int nr_run(int num_taps, float mu, const float *coeffs_init, const float *src, c
 }
 """
 
-# (name, num_taps, mu, calls): one long call against seven uneven calls of the same samples
+# (name, num_taps, mu, calls[, shaping]): one long call against seven uneven calls of the same samples; then (appended: every case draws from
+# the one seeded stream, so the arrays of the cases before it stay what they were) the edges of the arithmetic --
+#   ("gap", a, b, L): the signal, scaled by L, is exactly zero over samples a .. b - 1 -- a burst, silence, the signal back (the first edge inside a call, the
+#                  second on a call boundary).  In the silence `energy` is what the roundings of energy -= x0*x0, += in*in left: negative here
+#                  (tests/test_nr_oracle.py asserts it), so energy + eps is negative when the signal returns;
+#   ("level", L):  the signal scaled by L -- 1e-22: in*in and `energy` are denormals; 1e18: energy ~ 1e37, still finite;
+# and many calls shorter than the window (the copy-back of arm_lms_norm_f32.c:315-346 after one, two, three samples).
 CASES = [("t5_mu0.5", 5, 0.5, [600]), ("t8_mu0.01", 8, 0.01, [600]), ("t16_mu0.5", 16, 0.5, [600]),
          ("t32_mu1.5", 32, 1.5, [600]), ("t64_mu0.5", 64, 0.5, [600]), ("t32_mu0.5_one", 32, 0.5, [1000]),
-         ("t32_mu0.5_seven", 32, 0.5, [1, 7, 64, 129, 300, 3, 496]), ("t64_mu0.01_seven", 64, 0.01, [33, 5, 200, 62, 250, 1, 49])]
+         ("t32_mu0.5_seven", 32, 0.5, [1, 7, 64, 129, 300, 3, 496]), ("t64_mu0.01_seven", 64, 0.01, [33, 5, 200, 62, 250, 1, 49]),
+         ("t8_mu0.05_gap", 8, 0.05, [250, 200, 150, 400], ("gap", 300, 600, 1.0)),
+         ("t64_mu1.5_gap", 64, 1.5, [250, 200, 150, 400], ("gap", 300, 600, 1.5)),
+         ("t32_mu0.5_lvl1e-22", 32, 0.5, [500, 500], ("level", 1e-22)), ("t32_mu0.5_lvl1e18", 32, 0.5, [500, 500], ("level", 1e18)),
+         ("t16_mu0.5_short", 16, 0.5, [1, 1, 2, 3, 12, 24, 5, 36, 1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 4, 60, 63, 64, 65, 2, 24, 24, 12, 48, 96, 1, 100, 23, 25, 61])]
 SEED = 0x4C4D53
 
 
@@ -68,11 +78,16 @@ def main(ref_root):
         fp = C.POINTER(C.c_float)
         L.nr_run.argtypes = [C.c_int, C.c_float, fp, fp, fp, C.c_int, C.POINTER(C.c_int), fp, fp, fp, fp, fp]
         rng = np.random.default_rng(SEED)
-        for ci, (name, n, mu, lens) in enumerate(CASES):
+        for ci, (name, n, mu, lens, *shaping) in enumerate(CASES):
             total = sum(lens)
             t = np.arange(total + 64)
             # a tone plus noise; pSrc is pRef delayed by 3 samples (the stage's shape)
             x = (0.6 * np.sin(2 * np.pi * 0.031 * t + ci) + 0.2 * rng.standard_normal(total + 64)).astype(np.float32)
+            if shaping and shaping[0][0] == "gap":
+                x = x * np.float32(shaping[0][3])
+                x[64 + shaping[0][1]:64 + shaping[0][2]] = 0.0
+            if shaping and shaping[0][0] == "level":
+                x = x * np.float32(shaping[0][1])
             ref, src = x[64:].copy(), x[61:61 + total].copy()
             init = (0.01 * rng.standard_normal(n)).astype(np.float32) if ci % 2 else np.zeros(n, np.float32)
             y, e = np.empty(total, np.float32), np.empty(total, np.float32)

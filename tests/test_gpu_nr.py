@@ -50,6 +50,29 @@ def oracle_chain(spec):
     return rc.CpuChain(s, "orc")
 
 
+class GlobalGain:
+    """The AGC law of nr_oracle.Agc with ONE gain for all channels: per DSP block the envelope is taken over every channel (agc_global)."""
+
+    def __init__(self, spec):
+        self.p = {k: np.float32(v) for k, v in spec.agc_params.items()}
+        self.g, self.na = self.p["gain_init"], spec.block // spec.decim
+
+    def process(self, y):
+        p, g, na = self.p, self.g, self.na
+        want = np.empty_like(y)
+        for b0 in range(0, y.shape[1], na):                    # one gain from the envelope over ALL channels
+            env = np.float32(np.max(np.abs(y[:, b0:b0 + na])))
+            e = p["env_floor"] if env < p["env_floor"] else env
+            dd = np.float32(p["target"] / e)
+            dd = p["gain_max"] if dd > p["gain_max"] else dd
+            dd = p["gain_min"] if dd < p["gain_min"] else dd
+            diff = np.float32(dd - g)
+            g = np.float32(g + np.float32((p["attack"] if diff < 0 else p["decay"]) * diff))
+            want[:, b0:b0 + na] = y[:, b0:b0 + na] * g
+        self.g = g
+        return want
+
+
 def assert_bits(got, want, what=""):
     assert got.shape == want.shape, (what, got.shape, want.shape)
     if got.tobytes() != want.tobytes():
@@ -265,9 +288,8 @@ def test_global_gain_phase1_phase2_matches_restatement():
     a, b = sr.Rx(sa.config()), sr.Rx(sb.config())
     a.set_nr(sr.NR_DENOISE, num_taps=32, delay=16, mu=0.05)
     nl = nro.Nlms(ch, 32, 0.05, delay=16)
-    p = {k: np.float32(v) for k, v in sa.agc_params.items()}
-    g = p["gain_init"]
-    nout, na = bs // 4, 64
+    gg = GlobalGain(sa)
+    nout = bs // 4
     d_in, d_out, d_env = sr.DeviceBuffer(ch * bs * 8), sr.DeviceBuffer(ch * nout * 4), sr.DeviceBuffer(4 * (bs // 256))
     for call in range(2):
         iq = rc.synth_iq(0, ch, call * bs, bs)
@@ -277,16 +299,7 @@ def test_global_gain_phase1_phase2_matches_restatement():
         a.global_phase2(d_out.ptr, d_env.ptr, bs)
         a.sync()
         got = d_out.download((ch, nout), np.float32)
-        want = np.empty_like(y)
-        for b0 in range(0, nout, na):                          # one gain from the envelope over ALL channels
-            env = np.float32(np.max(np.abs(y[:, b0:b0 + na])))
-            e = p["env_floor"] if env < p["env_floor"] else env
-            dd = np.float32(p["target"] / e)
-            dd = p["gain_max"] if dd > p["gain_max"] else dd
-            dd = p["gain_min"] if dd < p["gain_min"] else dd
-            diff = np.float32(dd - g)
-            g = np.float32(g + np.float32((p["attack"] if diff < 0 else p["decay"]) * diff))
-            want[:, b0:b0 + na] = y[:, b0:b0 + na] * g
+        want = gg.process(y)
         assert_bits(got, want, "call %d" % call)
 
 

@@ -33,6 +33,20 @@ def test_fixture_covers_the_issue_cases():
     assert taps == {5, 8, 16, 32, 64}
     assert {0.01, 0.5, 1.5} <= {round(m, 6) for m in mus}
     assert any(len(GOLDEN[c + "/lens"]) == 7 for c in GOLDEN["cases"])
+    # the edges of the arithmetic (tests/test_gpu_nr_edges.py rests on the restatement there)
+    cases = {str(c): {k.split("/", 1)[1]: GOLDEN[k] for k in GOLDEN.files if k.startswith(str(c) + "/")} for c in GOLDEN["cases"]}
+    tiny = np.finfo(np.float32).tiny
+    gaps = [g for g in cases.values() if (g["ref"] == 0).sum() >= 200 and g["ref"][:100].any() and g["ref"][-100:].any()]
+    assert {8, 64} <= {int(g["num_taps"]) for g in gaps}                                      # burst, exact silence, the signal back
+    for g in gaps:                                                                            # ... with a negative energy when it comes back
+        st = nro.Nlms(1, int(g["num_taps"]), float(g["mu"]), g["coeffs_init"])
+        n = int(np.flatnonzero(g["ref"] == 0).max()) + 1                                      # (a call boundary: the generator's ("gap", a, b, L))
+        assert n in np.cumsum(g["lens"]) and int(np.flatnonzero(g["ref"] == 0).min()) not in np.cumsum(g["lens"])
+        st.lms(g["src"][None, :n], g["ref"][None, :n])
+        assert st.energy[0] < 0 and not g["src"][n - int(g["num_taps"]) - 1:n].any()
+    assert any(0 < abs(float(g["energy"][0])) < tiny for g in cases.values())                # a denormal energy (level 1e-22)
+    assert any(1e17 < np.abs(g["ref"]).max() < 1e19 and np.isfinite(g["y"]).all() and np.isfinite(g["coeffs"]).all() for g in cases.values())
+    assert any(len(g["lens"]) >= 30 and min(g["lens"]) == 1 and {12, 24, 36} <= set(g["lens"].tolist()) for g in cases.values())   # many short calls
 
 
 def test_restatement_is_vectorised_per_channel():
