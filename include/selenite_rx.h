@@ -30,6 +30,7 @@
  *   -> arm_biquad_cascade_df1_f32 (CW narrow filter)
  *   -> [optional: arm_lms_norm_f32 noise reduction / automatic notch, selenite_rx_set_nr]
  *   -> arm_abs_f32 + arm_max_f32 -> gain law -> arm_scale_f32 (AGC)
+ *   -> [optional: arm_fir_interpolate_f32 back to the slot rate, mono / stereo frames, selenite_rx_set_out]
  */
 #ifndef SELENITE_RX_H
 #define SELENITE_RX_H
@@ -197,6 +198,27 @@ typedef struct selenite_rx_nr_state_view {
     float *x0;
 } selenite_rx_nr_state_view;
 
+/* ---- audio output stage (step 7 of DESIGN.md section 2, behind the AGC; off by default) ---------------------------------------
+ * What DSP_Out_Buff_Read (Core/Src/dsp_if.c:204-219) hands the codec: the audio back at the slot rate, as left / right frames.
+ * Per channel and DSP block of n = block / decim audio samples:
+ *   arm_fir_interpolate_f32(L, coeffs, ni_taps)   n in, n * L out (FilteringFunctions/arm_fir_interpolate_f32.c:136-563)
+ *   int16 slots: arm_float_to_q15 on the interpolated samples (cfg.q15_rounding)
+ *   SELENITE_RX_OUT_MONO one value per sample; SELENITE_RX_OUT_STEREO each value twice, left then right (pbuf[k] = i, pbuf[k + 1] = q)
+ * With the stage on, pDstAudio of every process entry point is [channels][blockSize / decim * L * (STEREO ? 2 : 1)]
+ * (selenite_rx_out_values per channel).  The stage keeps the reference's rounding in every arith mode (one accumulator per output from
+ * +0.0f, taps ascending, product rounded, then sum rounded): given its input it is bit-exact against arm_fir_interpolate_f32.
+ * Non-finite stage output raises SELENITE_RX_NANINF like any other. */
+#define SELENITE_RX_OUT_MONO   0
+#define SELENITE_RX_OUT_STEREO 1
+
+typedef struct selenite_rx_out_config {
+    uint32_t struct_size;     /* = sizeof(selenite_rx_out_config) (this struct's own growth path) */
+    uint32_t interp;          /* L: 1, 2, 4 or 8 (need not equal cfg.decim) */
+    uint32_t ni_taps;         /* L * P, P = phaseLength 1 .. 64; interp == 1 && ni_taps == 0: no FIR, frames only */
+    uint32_t frames;          /* SELENITE_RX_OUT_* */
+    const float *coeffs;      /* [ni_taps] pCoeffs order {b[numTaps-1] .. b[0]} (arm_fir_interpolate_f32.c:63-72); finite; copied */
+} selenite_rx_out_config;
+
 typedef struct selenite_rx_instance selenite_rx_instance;  /* opaque; state lives in HBM */
 
 /* ---- instance life cycle ------------------------------------------------------------- */
@@ -336,6 +358,22 @@ int  selenite_rx_set_nr(selenite_rx_instance *S, const selenite_rx_nr_config *nr
 int  selenite_rx_get_nr_state(selenite_rx_instance *S, const selenite_rx_nr_state_view *dst);
 int  selenite_rx_set_nr_state(selenite_rx_instance *S, const selenite_rx_nr_state_view *src);
 
+/* ---- audio output stage ------------------------------------------------------------------ */
+
+/* Mirrors arm_fir_interpolate_init_f32 (FilteringFunctions/arm_fir_interpolate_init_f32.c:91-96) for every channel: ni_taps % interp != 0 is
+ * a SELENITE_RX_LENGTH_ERROR, any other field out of range a SELENITE_RX_ARGUMENT_ERROR, and the instance is left as it was.  Clears the
+ * stage's state and nothing else; out == NULL removes the stage.  selenite_rx_set_mode and selenite_rx_set_nr leave the stage alone,
+ * selenite_rx_reset clears its state with the rest.  Every process entry point runs it (f32 and int16 slots, device and host pointers, the
+ * timing calls, selenite_rx_global_process_f32_device behind phase 2); selenite_rx_global_phase1_device / _phase2_device exchange audio
+ * at the decimated rate by contract: with a stage set they raise a sticky SELENITE_RX_ARGUMENT_ERROR and touch nothing. */
+int      selenite_rx_set_out(selenite_rx_instance *S, const selenite_rx_out_config *out);
+/* values per channel a process call of blockSize writes to pDstAudio (blockSize / decim without a stage) */
+uint32_t selenite_rx_out_values(const selenite_rx_instance *S, uint32_t blockSize);
+/* interp_state [channels][P - 1]: the last P - 1 audio samples, oldest first (arm_fir_interpolate_f32.c:433-475 copy-back order).
+ * SELENITE_RX_ARGUMENT_ERROR while the stage is off, or with P <= 1 (nothing to keep). */
+int      selenite_rx_get_out_state(selenite_rx_instance *S, float *interp_state);
+int      selenite_rx_set_out_state(selenite_rx_instance *S, const float *interp_state);
+
 void *selenite_rx_device_alloc(size_t bytes);          /* hipMalloc; NULL on failure */
 void  selenite_rx_device_free(void *dptr);
 int   selenite_rx_memcpy_h2d(void *dptr, const void *hptr, size_t bytes);
@@ -430,6 +468,10 @@ int selenite_rx_design_hilbert(float *hilb, float *delay, uint32_t num_taps);
 /* n_stages identical RBJ constant-peak band-pass sections centred on f0 (fraction of the
  * sample rate) with quality factor q; coefficients in CMSIS sign convention (+a1, +a2). */
 int selenite_rx_design_bandpass(float *coeffs, uint32_t n_stages, double f0, double q);
+
+/* The interpolation low-pass of the output stage: selenite_rx_design_lowpass(ni_taps, cutoff) times `interp` (the pass-band level survives
+ * the zero stuffing); cutoff as a fraction of the OUTPUT sample rate; interp 1, 2, 4 or 8 dividing ni_taps. */
+int selenite_rx_design_interp(float *coeffs, uint32_t ni_taps, uint32_t interp, double cutoff);
 
 int selenite_rx_abi_version(void);
 

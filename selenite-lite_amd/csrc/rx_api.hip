@@ -115,7 +115,8 @@ static void free_device(selenite_rx_instance *S)
     void *ptrs[] = { S->d_flags, S->d_guard_ch, S->d_rerun_flag, S->d_rerun_list, S->d_hist_ext, S->d_conv_in, S->d_dec_c, S->d_hilb_c, S->d_delay_c, S->d_biq_c, S->d_sintab, S->d_step, S->d_phase,
                      S->d_dec_state, S->d_fir_state, S->d_biq_state, S->d_gain, S->d_scratch, S->d_env, S->d_env_part,
                      S->d_io_in, S->d_io_out, S->d_lo, S->pipe.d_in[0], S->pipe.d_in[1], S->pipe.d_out[0], S->pipe.d_out[1],
-                     S->d_nr_coeffs, S->d_nr_window, S->d_nr_delay, S->d_nr_energy, S->d_nr_x0 };
+                     S->d_nr_coeffs, S->d_nr_window, S->d_nr_delay, S->d_nr_energy, S->d_nr_x0,
+                     S->d_out_coeffs, S->d_out_state, S->d_out_audio };
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (S->h_rerun_seen) (void)hipHostFree(S->h_rerun_seen);
@@ -149,6 +150,16 @@ static int nr_init_state(selenite_rx_instance *S)
     return SELENITE_RX_SUCCESS;
 }
 
+// the output stage's state as arm_fir_interpolate_init_f32 leaves it (arm_fir_interpolate_init_f32.c:101-104): cleared
+static int out_init_state(selenite_rx_instance *S)
+{
+    if (!S->out_on || S->out_taps / S->out_interp < 2) return SELENITE_RX_SUCCESS;
+    const size_t n = (size_t)S->cfg.channels * (S->out_taps / S->out_interp - 1);
+    HIPCHK(S, hipMemsetAsync(S->d_out_state, 0, n * sizeof(float), S->stream));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    return SELENITE_RX_SUCCESS;
+}
+
 static int reset_state(selenite_rx_instance *S)
 {
     const selenite_rx_config &g = S->cfg;
@@ -168,7 +179,8 @@ static int reset_state(selenite_rx_instance *S)
     HIPCHK(S, hipStreamSynchronize(S->stream));
     S->phase_uniform = true;
     S->phase_host = 0;
-    return nr_init_state(S);
+    if (int rc = nr_init_state(S)) return rc;
+    return out_init_state(S);
 }
 
 // the kernels' flag word (non-finite audio: ARM_MATH_NANINF), read after the stream has drained; latches the status
@@ -652,6 +664,80 @@ extern "C" int selenite_rx_set_nr_state(selenite_rx_instance *S, const selenite_
     return SELENITE_RX_SUCCESS;
 }
 
+// ---- audio output stage (rx_out.hip) ----
+static void out_release(selenite_rx_instance *S)
+{
+    float **bufs[] = { &S->d_out_coeffs, &S->d_out_state, &S->d_out_audio };
+    for (float **b : bufs) {
+        if (*b) (void)hipFree(*b);
+        *b = nullptr;
+    }
+    S->out_audio_bytes = 0;
+    S->out_on = false;
+    S->out_interp = 1; S->out_taps = 0; S->out_frames = SELENITE_RX_OUT_MONO;
+}
+
+extern "C" int selenite_rx_set_out(selenite_rx_instance *S, const selenite_rx_out_config *out)
+{
+    if (!S) return fail(nullptr, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_set_out: S is NULL");
+    // everything is validated before anything changes: a refused call leaves the instance as it was
+    if (out) {
+        const uint32_t L = out->interp;
+        const char *bad = nullptr;
+        int code = SELENITE_RX_ARGUMENT_ERROR;
+        if (out->struct_size != sizeof(selenite_rx_out_config)) bad = "struct_size is not sizeof(selenite_rx_out_config)";
+        else if (L != 1 && L != 2 && L != 4 && L != 8) bad = "interp is not 1, 2, 4 or 8";
+        else if (out->ni_taps % L != 0) { bad = "ni_taps is not a multiple of interp"; code = SELENITE_RX_LENGTH_ERROR; }   // arm_fir_interpolate_init_f32.c:91-96
+        else if (out->ni_taps / L > 64 || (out->ni_taps == 0 && L != 1)) bad = "ni_taps / interp is not 1 .. 64 (0 taps: interp 1 only)";
+        else if (out->frames != SELENITE_RX_OUT_MONO && out->frames != SELENITE_RX_OUT_STEREO) bad = "frames is not a SELENITE_RX_OUT_* value";
+        else if (out->ni_taps && !out->coeffs) bad = "coeffs is NULL";
+        else
+            for (uint32_t k = 0; k < out->ni_taps && !bad; ++k)
+                if (!std::isfinite(out->coeffs[k])) bad = "coeffs holds a non-finite tap";
+        if (bad) {
+            g_last_error = std::string("selenite_rx_set_out: ") + bad;
+            return code;
+        }
+    }
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    out_release(S);
+    if (!out) return SELENITE_RX_SUCCESS;
+    const size_t C = S->cfg.channels, P = out->ni_taps / out->interp;
+    hipError_t e = hipSuccess;
+    if (out->ni_taps) e = dev_upload(&S->d_out_coeffs, out->coeffs, (size_t)out->ni_taps);
+    if (e == hipSuccess && P > 1) e = hipMalloc((void **)&S->d_out_state, C * (P - 1) * sizeof(float));
+    if (e != hipSuccess) {
+        out_release(S);
+        return fail(S, SELENITE_RX_DEVICE_ERROR, std::string("selenite_rx_set_out: hipMalloc: ") + hipGetErrorString(e));
+    }
+    S->out_on = true; S->out_interp = out->interp; S->out_taps = out->ni_taps; S->out_frames = out->frames;
+    return out_init_state(S);
+}
+
+extern "C" uint32_t selenite_rx_out_values(const selenite_rx_instance *S, uint32_t blockSize)
+{
+    if (!S) return 0;
+    const uint32_t n = blockSize / S->cfg.decim;
+    return S->out_on ? n * S->out_interp * (S->out_frames == SELENITE_RX_OUT_STEREO ? 2u : 1u) : n;
+}
+
+static int out_state_copy(selenite_rx_instance *S, float *host, bool to_host)
+{
+    if (!S || !host || !S->out_on || S->out_taps / S->out_interp < 2) return SELENITE_RX_ARGUMENT_ERROR;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    const size_t bytes = (size_t)S->cfg.channels * (S->out_taps / S->out_interp - 1) * sizeof(float);
+    if (to_host) HIPCHK(S, hipMemcpy(host, S->d_out_state, bytes, hipMemcpyDeviceToHost));
+    else HIPCHK(S, hipMemcpy(S->d_out_state, host, bytes, hipMemcpyHostToDevice));
+    return SELENITE_RX_SUCCESS;
+}
+extern "C" int selenite_rx_get_out_state(selenite_rx_instance *S, float *interp_state) { return out_state_copy(S, interp_state, true); }
+extern "C" int selenite_rx_set_out_state(selenite_rx_instance *S, const float *interp_state)
+{
+    return out_state_copy(S, const_cast<float *>(interp_state), false);
+}
+
 // ------------------------------------------------------------------------------------------
 static RxParams make_params(selenite_rx_instance *S, uint32_t block_size)
 {
@@ -889,8 +975,8 @@ static int run_part(selenite_rx_instance *S, const void *src, bool src_q15, void
 // split-precision call that ends in a partial pass too short for the matrix kernel is cut in two launches on the same
 // streaming state (fused_tail_split; both parts address the caller's buffers with the full per-channel stride; in
 // SELENITE_ARITH_AUTO the tail runs in the bit-exact arithmetic, rx_fused.hip launch_shape).
-static int run_chain(selenite_rx_instance *S, const void *src, bool src_q15, void *dst, bool dst_q15,
-                     uint32_t block_size, Phase phase, float *ext_env)
+static int run_chain_core(selenite_rx_instance *S, const void *src, bool src_q15, void *dst, bool dst_q15,
+                          uint32_t block_size, Phase phase, float *ext_env)
 {
     const selenite_rx_config &g = S->cfg;
     const uint32_t nout = block_size / g.decim;
@@ -907,6 +993,55 @@ static int run_chain(selenite_rx_instance *S, const void *src, bool src_q15, voi
         }
     }
     return run_part(S, src, src_q15, dst, dst_q15, block_size, phase, ext_env, block_size, nout);
+}
+
+// ---- the output stage around the chain (step 7) ----
+// the instance-owned f32 audio the chain writes in front of the stage: [channels of the launch][block_size / decim], grown, never per call
+static int out_audio(selenite_rx_instance *S, uint32_t block_size, float **audio)
+{
+    const size_t nch = S->sub_count ? S->sub_count : S->cfg.channels;
+    int rc = ensure(S, (void **)&S->d_out_audio, &S->out_audio_bytes, nch * (block_size / S->cfg.decim) * sizeof(float));
+    *audio = S->d_out_audio;
+    return rc;
+}
+// the stage kernel, once over the whole call: `audio` (out_audio) -> the caller's dst
+static int out_finish(selenite_rx_instance *S, const float *audio, void *dst, bool dst_q15, uint32_t block_size)
+{
+    OutParams q{};
+    q.channels = S->sub_count ? S->sub_count : S->cfg.channels;
+    q.nout = block_size / S->cfg.decim; q.stride = q.nout;
+    q.phase_len = S->out_taps / S->out_interp;
+    q.q15_round = S->cfg.q15_rounding ? 1u : 0u;
+    const bool stereo = S->out_frames == SELENITE_RX_OUT_STEREO;
+    const size_t row_bytes = (size_t)q.nout * S->out_interp * out_sample_bytes(stereo, dst_q15);
+    q.vec = (reinterpret_cast<uintptr_t>(dst) % 16 == 0 && row_bytes % 16 == 0) ? 1u : 0u;
+    q.coeffs = S->d_out_coeffs;
+    q.state = S->d_out_state;
+    if (q.state && S->sub_count) q.state += (size_t)S->sub_first * (q.phase_len - 1);   // a channel range of the instance (make_params)
+    q.flags = S->d_flags;
+    HIPCHK(S, launch_out(q, S->out_interp, stereo, dst_q15, audio, dst, S->stream));
+    return SELENITE_RX_SUCCESS;
+}
+
+// With a stage the chain runs exactly as without one, into the instance's f32 audio buffer, and the stage kernel writes the caller's dst.
+// int16 slots: the fused kernels convert in and out symmetrically, so the input is converted up front (arm_q15_to_float over the whole
+// buffer, the operation the fused int16 load performs) and the call runs as an f32 call whose stage stores int16.
+static int run_chain(selenite_rx_instance *S, const void *src, bool src_q15, void *dst, bool dst_q15,
+                     uint32_t block_size, Phase phase, float *ext_env)
+{
+    if (!S->out_on) return run_chain_core(S, src, src_q15, dst, dst_q15, block_size, phase, ext_env);
+    if (phase != kAll) return fail(S, SELENITE_RX_ARGUMENT_ERROR, "the split global-gain calls exchange audio at the decimated rate: not with an output stage");
+    HIPCHK(S, hipSetDevice(S->device));
+    float *audio = nullptr;
+    if (int rc = out_audio(S, block_size, &audio)) return rc;
+    if (src_q15) {
+        const size_t nval = (size_t)(S->sub_count ? S->sub_count : S->cfg.channels) * block_size * 2;
+        if (int rc = ensure(S, (void **)&S->d_conv_in, &S->conv_in_bytes, nval * sizeof(float))) return rc;
+        HIPCHK(S, launch_q15_to_f32_any(static_cast<const int16_t *>(src), S->d_conv_in, nval, S->stream));
+        src = S->d_conv_in;
+    }
+    if (int rc = run_chain_core(S, src, false, audio, false, block_size, kAll, nullptr)) return rc;
+    return out_finish(S, audio, dst, dst_q15, block_size);
 }
 
 extern "C" void selenite_rx_process_f32_device(selenite_rx_instance *S, const float *dSrcIQ,
@@ -931,6 +1066,10 @@ extern "C" void selenite_rx_global_phase1_device(selenite_rx_instance *S, const 
         fail(S, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_global_phase1_device: instance is not agc_global");
         return;
     }
+    if (S->out_on) {
+        fail(S, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_global_phase1_device: the split calls exchange audio at the decimated rate: not with an output stage (selenite_rx_set_out)");
+        return;
+    }
     run_chain(S, dSrcIQ, false, dDstAudio, false, blockSize, kPhase1, dEnv);
 }
 
@@ -940,6 +1079,10 @@ extern "C" void selenite_rx_global_phase2_device(selenite_rx_instance *S, float 
     if (!S || !block_size_ok(S, blockSize, "selenite_rx_global_phase2_device")) return;
     if (!(S->cfg.agc_enable && S->cfg.agc_global)) {
         fail(S, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_global_phase2_device: instance is not agc_global");
+        return;
+    }
+    if (S->out_on) {
+        fail(S, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_global_phase2_device: the split calls exchange audio at the decimated rate: not with an output stage (selenite_rx_set_out)");
         return;
     }
     run_chain(S, nullptr, false, dDstAudio, false, blockSize, kPhase2, const_cast<float *>(dEnv));
@@ -973,7 +1116,10 @@ extern "C" int selenite_rx_global_process_f32_device(selenite_rx_instance *S, co
     const size_t nblk = blockSize / S->cfg.block;
     int rc = ensure(S, (void **)&S->d_env, &S->env_cap, sizeof(float) * nblk);
     if (rc) return rc;
-    rc = run_chain(S, dSrcIQ, false, dDstAudio, false, blockSize, kPhase1, S->d_env);
+    // (an output stage sits behind phase 2: both phases work on the instance's audio buffer, the stage writes dDstAudio)
+    float *audio = dDstAudio;
+    if (S->out_on && (rc = out_audio(S, blockSize, &audio))) return rc;
+    rc = run_chain_core(S, dSrcIQ, false, audio, false, blockSize, kPhase1, S->d_env);
     if (rc) return rc;
     if (rccl_comm) {                                        // NULL: single rank, nothing to exchange
         nccl_allreduce_fn ar = rccl_allreduce();
@@ -982,7 +1128,9 @@ extern "C" int selenite_rx_global_process_f32_device(selenite_rx_instance *S, co
         const int e = ar(S->d_env, S->d_env, nblk, nccl_float, nccl_max, rccl_comm, S->stream);
         if (e != 0) return fail(S, SELENITE_RX_DEVICE_ERROR, "selenite_rx_global_process_f32_device: ncclAllReduce failed (" + std::to_string(e) + ")");
     }
-    return run_chain(S, nullptr, false, dDstAudio, false, blockSize, kPhase2, S->d_env);
+    rc = run_chain_core(S, nullptr, false, audio, false, blockSize, kPhase2, S->d_env);
+    if (rc || !S->out_on) return rc;
+    return out_finish(S, audio, dDstAudio, false, blockSize);
 }
 
 // ---- host-pointer entry points: the literal drop-in signature (float* / int16_t* I/Q in, audio out) ----
@@ -1056,7 +1204,7 @@ static void process_host(selenite_rx_instance *S, const void *src, void *dst, ui
     if (!S || !block_size_ok(S, block_size, who)) return;
     const selenite_rx_config &g = S->cfg;
     const size_t esz = q15 ? sizeof(int16_t) : sizeof(float);
-    const size_t in_ch = (size_t)block_size * 2 * esz, out_ch = (size_t)(block_size / g.decim) * esz;   // bytes per channel
+    const size_t in_ch = (size_t)block_size * 2 * esz, out_ch = (size_t)selenite_rx_out_values(S, block_size) * esz;   // bytes per channel
     if (hipSetDevice(S->device) != hipSuccess) { fail(S, SELENITE_RX_DEVICE_ERROR, "hipSetDevice"); return; }
 
     if (g.agc_enable && g.agc_global) {                     // one chunk: every envelope before any gain

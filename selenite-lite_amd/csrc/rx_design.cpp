@@ -33,6 +33,16 @@ extern "C" int selenite_rx_design_lowpass(float *coeffs, uint32_t num_taps, doub
     return SELENITE_RX_SUCCESS;
 }
 
+extern "C" int selenite_rx_design_interp(float *coeffs, uint32_t ni_taps, uint32_t interp, double cutoff)
+{
+    if (interp != 1 && interp != 2 && interp != 4 && interp != 8) return SELENITE_RX_ARGUMENT_ERROR;
+    if (ni_taps % interp != 0) return SELENITE_RX_LENGTH_ERROR;          // arm_fir_interpolate_init_f32.c:91-96
+    const int rc = selenite_rx_design_lowpass(coeffs, ni_taps, cutoff);
+    if (rc != SELENITE_RX_SUCCESS) return rc;
+    for (uint32_t n = 0; n < ni_taps; ++n) coeffs[n] = coeffs[n] * (float)interp;
+    return SELENITE_RX_SUCCESS;
+}
+
 extern "C" int selenite_rx_design_hilbert(float *hilb, float *delay, uint32_t num_taps)
 {
     if (!hilb || !delay || num_taps < 3 || (num_taps % 2) == 0) return SELENITE_RX_ARGUMENT_ERROR;

@@ -152,6 +152,24 @@ struct NrParams {
 };
 hipError_t launch_nlms(const NrParams &q, uint32_t num_taps, float *audio, hipStream_t st);
 
+// ---- audio output stage (rx_out.hip): arm_fir_interpolate_f32 -> [arm_float_to_q15] -> mono / stereo frames, behind the AGC ----
+struct OutParams {
+    uint32_t channels;     // channels of this launch (a sub-range on the host-pointer path: `state` is offset to it)
+    uint32_t nout;         // audio samples per channel in this call (input of the stage)
+    uint32_t stride;       // audio samples between consecutive channels of `audio`
+    uint32_t phase_len;    // P = ni_taps / interp; 0: no FIR (interp == 1), the samples pass as they are
+    uint32_t q15_round;    // int16 output: RxParams::q15_round
+    uint32_t vec;          // 1: dst and every row of it are 16-byte aligned -- whole 16-byte stores per lane; 0: element stores
+    const float *coeffs;   // [interp * P] pCoeffs order
+    float *state;          // [C][P - 1] oldest first
+    uint32_t *flags;       // RxParams::flags (kFlagNanInf)
+};
+// bytes of one interpolated sample in dst
+inline uint32_t out_sample_bytes(bool stereo, bool q15) { return (q15 ? 2u : 4u) * (stereo ? 2u : 1u); }
+hipError_t launch_out(const OutParams &q, uint32_t interp, bool stereo, bool dst_q15, const float *audio, void *dst, hipStream_t st);
+// arm_q15_to_float over n values, any n (launch_q15_to_f32 wants whole groups of eight)
+hipError_t launch_q15_to_f32_any(const int16_t *src, float *dst, size_t n, hipStream_t st);
+
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
     int kind = 0;                 // 0 = none
@@ -271,6 +289,11 @@ struct selenite_rx_instance {
     float nr_mu = 0.0f;
     std::vector<float> h_nr_init;      // [nr_taps] the weights set_nr / reset start from
     float *d_nr_coeffs = nullptr, *d_nr_window = nullptr, *d_nr_delay = nullptr, *d_nr_energy = nullptr, *d_nr_x0 = nullptr;
+    // audio output stage (selenite_rx_set_out): out_on = false: no stage, no buffers
+    bool out_on = false;
+    uint32_t out_interp = 1, out_taps = 0, out_frames = SELENITE_RX_OUT_MONO;
+    float *d_out_coeffs = nullptr, *d_out_state = nullptr;    // [out_taps] | [channels][out_taps / out_interp - 1]
+    float *d_out_audio = nullptr; size_t out_audio_bytes = 0;   // f32 audio of the chain in front of the stage, [channels][blockSize / decim]
     int status = SELENITE_RX_SUCCESS;
     std::string err;
 };

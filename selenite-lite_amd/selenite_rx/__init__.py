@@ -22,6 +22,7 @@ ABI_VERSION, CONFIG_SIZE_V1, TX_CONFIG_SIZE_V1 = 2, 112, 96      # include/selen
 OPT_FORCE_GENERIC, OPT_NO_SHARED_LO, OPT_NO_PERIODIC_LO, OPT_RERUN_GRID, OPT_TX_FORCE_GENERIC, OPT_CW_GRID = 0, 1, 2, 3, 4, 5      # selenite_rx_set_plan_option
 SUCCESS, ARGUMENT_ERROR, LENGTH_ERROR, NANINF, DEVICE_ERROR = 0, -1, -2, -4, -7
 NR_OFF, NR_DENOISE, NR_NOTCH = 0, 1, 2                         # selenite_rx_set_nr: the NLMS stage's kind
+OUT_MONO, OUT_STEREO = 0, 1                                    # selenite_rx_set_out: the output stage's frame format
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -62,6 +63,12 @@ class NrStateView(C.Structure):
     _fields_ = [("coeffs", f32p), ("window", f32p), ("delay", f32p), ("energy", f32p), ("x0", f32p)]
 
 
+class OutConfig(C.Structure):
+    """struct selenite_rx_out_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("interp", C.c_uint32), ("ni_taps", C.c_uint32), ("frames", C.c_uint32),
+                ("coeffs", f32p)]
+
+
 # every symbol include/selenite_rx.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "selenite_rx_init", "selenite_rx_free", "selenite_rx_set_mode", "selenite_rx_status",
@@ -80,6 +87,7 @@ ABI_SYMBOLS = [
     "selenite_rx_time_process_each_device", "selenite_rx_time_streaming_roof_device", "selenite_rx_time_pattern_roof_device", "selenite_rx_device_pci_bus_id", "selenite_rx_set_plan_option", "selenite_rx_get_plan_option",
     "selenite_rx_set_guard_ratio", "selenite_rx_guard_stats", "selenite_rx_guard_channels", "selenite_rx_auto_words", "selenite_rx_guard_handover", "selenite_rx_set_handover_repair", "selenite_rx_set_auto_launches", "selenite_rx_auto_launches_last", "selenite_rx_guard_clear",
     "selenite_rx_set_nr", "selenite_rx_get_nr_state", "selenite_rx_set_nr_state",
+    "selenite_rx_set_out", "selenite_rx_out_values", "selenite_rx_get_out_state", "selenite_rx_set_out_state", "selenite_rx_design_interp",
 ]
 
 class TxConfig(C.Structure):
@@ -200,6 +208,13 @@ def lib():
             L.selenite_rx_set_nr.argtypes = [vp, C.POINTER(NrConfig)]
             L.selenite_rx_get_nr_state.argtypes = [vp, C.POINTER(NrStateView)]
             L.selenite_rx_set_nr_state.argtypes = [vp, C.POINTER(NrStateView)]
+        if hasattr(L, "selenite_rx_set_out"):               # (an older build named by SELENITE_RX_LIB lacks the output stage)
+            L.selenite_rx_set_out.argtypes = [vp, C.POINTER(OutConfig)]
+            L.selenite_rx_out_values.argtypes = [vp, C.c_uint32]
+            L.selenite_rx_out_values.restype = C.c_uint32
+            L.selenite_rx_get_out_state.argtypes = [vp, f32p]
+            L.selenite_rx_set_out_state.argtypes = [vp, f32p]
+            L.selenite_rx_design_interp.argtypes = [f32p, C.c_uint32, C.c_uint32, C.c_double]
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -222,6 +237,15 @@ def design_lowpass(num_taps, cutoff):
     rc = lib().selenite_rx_design_lowpass(_fp(h), num_taps, cutoff)
     if rc:
         raise ValueError("selenite_rx_design_lowpass: %d" % rc)
+    return h
+
+
+def design_interp(ni_taps, interp, cutoff):
+    """the output stage's interpolation low-pass: design_lowpass(ni_taps, cutoff) * interp, pCoeffs order"""
+    h = np.empty(ni_taps, np.float32)
+    rc = lib().selenite_rx_design_interp(_fp(h), ni_taps, interp, cutoff)
+    if rc:
+        raise ValueError("selenite_rx_design_interp: %d" % rc)
     return h
 
 
@@ -345,6 +369,9 @@ class Rx:
 
     # -- CMSIS-style calls ------------------------------------------------------------------
     def out_len(self, block_size):
+        """values per channel a call of block_size writes: block_size / decim, or what the output stage makes of it (out_values)"""
+        if getattr(self, "_out", None) is not None:
+            return self.out_values(block_size)
         return block_size // self.cfg.decim
 
     def process(self, iq, out=None):
@@ -591,6 +618,53 @@ class Rx:
         rc = self.L.selenite_rx_set_nr_state(self.h, C.byref(v))
         if rc:
             raise RxError(rc, "selenite_rx_set_nr_state")
+
+    # -- audio output stage (selenite_rx_set_out) ---------------------------------------------
+    def set_out(self, interp=1, coeffs=None, frames=OUT_MONO):
+        """Put the output stage behind the AGC -- arm_fir_interpolate_f32 by `interp` with `coeffs` (pCoeffs order; None with interp 1: no
+        FIR, frames only), mono or stereo frames -- or remove it (interp=None).  Clears the stage's state.  Raises RxError on a bad field;
+        the instance is then left as it was."""
+        old, self._out = getattr(self, "_out", None), None
+        if interp is None:
+            rc = self.L.selenite_rx_set_out(self.h, None)
+        else:
+            g = OutConfig()
+            g.struct_size = C.sizeof(OutConfig)
+            w = np.ascontiguousarray(coeffs if coeffs is not None else [], np.float32)
+            g.interp, g.ni_taps, g.frames = int(interp), int(w.size), int(frames)
+            g.coeffs = _fp(w) if w.size else None
+            rc = self.L.selenite_rx_set_out(self.h, C.byref(g))
+        if rc in (ARGUMENT_ERROR, LENGTH_ERROR):
+            self._out = old
+        if rc:
+            raise RxError(rc, self.L.selenite_rx_error_string(None).decode() if rc in (ARGUMENT_ERROR, LENGTH_ERROR) else self.error())
+        self._out = (int(interp), int(w.size) // int(interp), int(frames)) if interp is not None else None
+
+    def out_values(self, block_size):
+        """selenite_rx_out_values: values per channel a process call of block_size writes"""
+        if not hasattr(self.L, "selenite_rx_out_values"):      # (an older build named by SELENITE_RX_LIB: no stage)
+            return block_size // self.cfg.decim
+        return int(self.L.selenite_rx_out_values(self.h, block_size))
+
+    def _out_state_array(self):
+        if getattr(self, "_out", None) is None or self._out[1] < 2:
+            raise RxError(ARGUMENT_ERROR, "the output stage is off or keeps no state (phase length <= 1)")
+        return np.zeros((self.cfg.channels, self._out[1] - 1), np.float32)
+
+    def out_state(self):
+        """[channels][P - 1]: the interpolator's history, oldest first"""
+        a = self._out_state_array()
+        rc = self.L.selenite_rx_get_out_state(self.h, _fp(a))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_out_state")
+        return a
+
+    def set_out_state(self, state):
+        a = np.ascontiguousarray(state, np.float32)
+        assert a.shape == self._out_state_array().shape, a.shape
+        rc = self.L.selenite_rx_set_out_state(self.h, _fp(a))
+        if rc:
+            raise RxError(rc, "selenite_rx_set_out_state")
 
     def close(self):
         if self.h:
