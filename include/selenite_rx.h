@@ -219,6 +219,39 @@ typedef struct selenite_rx_out_config {
     const float *coeffs;      /* [ni_taps] pCoeffs order {b[numTaps-1] .. b[0]} (arm_fir_interpolate_f32.c:63-72); finite; copied */
 } selenite_rx_out_config;
 
+/* ---- spectrum tap (step 0b of DESIGN.md section 2, on the raw input I/Q in front of the NCO; off by default) -----------------------
+ * What the PC side of the reference draws: the power spectrum of the band, per channel.  The input stream (int16 slots through
+ * arm_q15_to_float) is cut into frames of fft_len consecutive complex samples -- frames of the STREAM, counted from set_spectrum / reset,
+ * not of the call: a partial frame waits in the instance.  Frame f is transformed iff f % stride == 0 (the others are never read):
+ *   arm_cmplx_mult_real_f32(frame, window)            ComplexMathFunctions/arm_cmplx_mult_real_f32.c (absent when window == NULL)
+ *   arm_cfft_f32(&arm_cfft_sR_f32_lenN, frame, 0, 1)  TransformFunctions/arm_cfft_f32.c:562-616, arm_cfft_radix8_f32.c:45-285: forward,
+ *                                                     natural-order output; fft_len 64 or 512, the pure radix-8 lengths
+ *   p = arm_cmplx_mag_squared_f32(frame)              ComplexMathFunctions/arm_cmplx_mag_squared_f32.c: re * re + im * im
+ *   average == 0: row[k] = p[k];  average == 1: row[k] = row[k] + alpha * (p[k] - row[k]) from row = +0.0f, every operation rounded
+ * The row is stored display-ordered: bin k at index (k + fft_len / 2) mod fft_len, DC in the middle.  Bit-exact against that composition
+ * in every arith mode (no contraction, no flushed denormals).  Non-finite power is stored as it comes and does NOT raise
+ * SELENITE_RX_NANINF: that status keeps meaning audio.  No dB: CMSIS-DSP 1.5.3 has no logarithm, the conversion is the display's. */
+#define SELENITE_RX_WINDOW_HANN            0
+#define SELENITE_RX_WINDOW_BLACKMAN_HARRIS 1
+
+typedef struct selenite_rx_spec_config {
+    uint32_t struct_size;     /* = sizeof(selenite_rx_spec_config) (this struct's own growth path) */
+    uint32_t fft_len;         /* N: 64 or 512; any other length is a SELENITE_RX_LENGTH_ERROR (arm_cfft_f32.c:582-599: radix8by2 / by4) */
+    uint32_t stride;          /* 1 .. 65535: every stride-th frame is transformed */
+    uint32_t average;         /* 0: the row is the last transformed frame's power; 1: exponential averaging with alpha */
+    float alpha;              /* 0 < alpha <= 1, finite */
+    const float *window;      /* [fft_len], finite, copied; NULL = none */
+} selenite_rx_spec_config;
+
+/* The tap's whole state.  rows [channels][fft_len] display order; pending [channels][fft_len][2]: the first position % fft_len samples
+ * of the frame the stream stands in (kept only for a frame that will be transformed); position: ONE value, input samples per channel
+ * since set_spectrum / reset.  NULL members are skipped. */
+typedef struct selenite_rx_spec_state_view {
+    float *rows;
+    float *pending;
+    uint64_t *position;
+} selenite_rx_spec_state_view;
+
 typedef struct selenite_rx_instance selenite_rx_instance;  /* opaque; state lives in HBM */
 
 /* ---- instance life cycle ------------------------------------------------------------- */
@@ -374,6 +407,27 @@ uint32_t selenite_rx_out_values(const selenite_rx_instance *S, uint32_t blockSiz
 int      selenite_rx_get_out_state(selenite_rx_instance *S, float *interp_state);
 int      selenite_rx_set_out_state(selenite_rx_instance *S, const float *interp_state);
 
+/* ---- spectrum tap ------------------------------------------------------------------------ */
+
+/* Sets the tap for every channel (selenite_rx_spec_config), or removes it (sp == NULL).  Clears the tap's state and nothing else.  A bad
+ * field (fft_len: SELENITE_RX_LENGTH_ERROR, any other: SELENITE_RX_ARGUMENT_ERROR) leaves the instance as it was, a working tap included.
+ * selenite_rx_set_mode, _set_nr and _set_out leave the tap alone; selenite_rx_reset clears rows, pending and position.  Every process
+ * entry point that has input runs it once per call (f32 and int16 slots, device and host pointers, the timing calls, global phase 1 --
+ * not phase 2).  With the tap off no launch, byte or output of any call changes. */
+int selenite_rx_set_spectrum(selenite_rx_instance *S, const selenite_rx_spec_config *sp);
+/* Host copy of the rows [channels][fft_len] (the state after the last transformed frame so far; +0.0f before the first) and the number
+ * of frames transformed since set_spectrum / reset; either pointer may be NULL.  Drains the instance's stream.
+ * SELENITE_RX_ARGUMENT_ERROR while the tap is off. */
+int selenite_rx_get_spectrum(selenite_rx_instance *S, float *rows, uint64_t *frames);
+/* The row buffer itself (device memory, [channels][fft_len]), for a consumer on the instance's stream; valid until the next
+ * selenite_rx_set_spectrum / selenite_rx_free.  NULL while the tap is off. */
+const float *selenite_rx_spectrum_device(const selenite_rx_instance *S);
+int selenite_rx_get_spectrum_state(selenite_rx_instance *S, const selenite_rx_spec_state_view *dst);   /* SELENITE_RX_ARGUMENT_ERROR while off */
+int selenite_rx_set_spectrum_state(selenite_rx_instance *S, const selenite_rx_spec_state_view *src);
+/* Host only, no device: the table the kernel uses, tw[fft_len][2] = (cos, sin)(2 pi i / fft_len) -- twiddleCoef_64 / twiddleCoef_512
+ * (CommonTables/arm_common_tables.c) entry for entry: each is the float of the nine-decimal rendering of the double value. */
+int selenite_rx_spectrum_twiddles(float *tw, uint32_t fft_len);
+
 void *selenite_rx_device_alloc(size_t bytes);          /* hipMalloc; NULL on failure */
 void  selenite_rx_device_free(void *dptr);
 int   selenite_rx_memcpy_h2d(void *dptr, const void *hptr, size_t bytes);
@@ -472,6 +526,10 @@ int selenite_rx_design_bandpass(float *coeffs, uint32_t n_stages, double f0, dou
 /* The interpolation low-pass of the output stage: selenite_rx_design_lowpass(ni_taps, cutoff) times `interp` (the pass-band level survives
  * the zero stuffing); cutoff as a fraction of the OUTPUT sample rate; interp 1, 2, 4 or 8 dividing ni_taps. */
 int selenite_rx_design_interp(float *coeffs, uint32_t ni_taps, uint32_t interp, double cutoff);
+
+/* A window for the spectrum tap, periodic form over n points (n >= 2): SELENITE_RX_WINDOW_HANN 0.5 - 0.5 cos(2 pi i / n), or
+ * SELENITE_RX_WINDOW_BLACKMAN_HARRIS (four terms, -92 dB side lobes). */
+int selenite_rx_design_window(float *w, uint32_t n, int kind);
 
 int selenite_rx_abi_version(void);
 

@@ -116,7 +116,8 @@ static void free_device(selenite_rx_instance *S)
                      S->d_dec_state, S->d_fir_state, S->d_biq_state, S->d_gain, S->d_scratch, S->d_env, S->d_env_part,
                      S->d_io_in, S->d_io_out, S->d_lo, S->pipe.d_in[0], S->pipe.d_in[1], S->pipe.d_out[0], S->pipe.d_out[1],
                      S->d_nr_coeffs, S->d_nr_window, S->d_nr_delay, S->d_nr_energy, S->d_nr_x0,
-                     S->d_out_coeffs, S->d_out_state, S->d_out_audio };
+                     S->d_out_coeffs, S->d_out_state, S->d_out_audio,
+                     S->d_spec_tw, S->d_spec_window, S->d_spec_rows, S->d_spec_pending };
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (S->h_rerun_seen) (void)hipHostFree(S->h_rerun_seen);
@@ -160,6 +161,18 @@ static int out_init_state(selenite_rx_instance *S)
     return SELENITE_RX_SUCCESS;
 }
 
+// the spectrum tap's state as set_spectrum leaves it: rows +0.0f, no pending samples, position 0
+static int spec_init_state(selenite_rx_instance *S)
+{
+    if (!S->spec_len) return SELENITE_RX_SUCCESS;
+    const size_t n = (size_t)S->cfg.channels * S->spec_len;
+    HIPCHK(S, hipMemsetAsync(S->d_spec_rows, 0, n * sizeof(float), S->stream));
+    HIPCHK(S, hipMemsetAsync(S->d_spec_pending, 0, 2 * n * sizeof(float), S->stream));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    S->spec_pos = 0;
+    return SELENITE_RX_SUCCESS;
+}
+
 static int reset_state(selenite_rx_instance *S)
 {
     const selenite_rx_config &g = S->cfg;
@@ -180,7 +193,8 @@ static int reset_state(selenite_rx_instance *S)
     S->phase_uniform = true;
     S->phase_host = 0;
     if (int rc = nr_init_state(S)) return rc;
-    return out_init_state(S);
+    if (int rc = out_init_state(S)) return rc;
+    return spec_init_state(S);
 }
 
 // the kernels' flag word (non-finite audio: ARM_MATH_NANINF), read after the stream has drained; latches the status
@@ -738,6 +752,94 @@ extern "C" int selenite_rx_set_out_state(selenite_rx_instance *S, const float *i
     return out_state_copy(S, const_cast<float *>(interp_state), false);
 }
 
+// ---- spectrum tap (rx_spectrum.hip) ----
+static void spec_release(selenite_rx_instance *S)
+{
+    float **bufs[] = { &S->d_spec_tw, &S->d_spec_window, &S->d_spec_rows, &S->d_spec_pending };
+    for (float **b : bufs) {
+        if (*b) (void)hipFree(*b);
+        *b = nullptr;
+    }
+    S->spec_len = 0; S->spec_stride = 1; S->spec_average = 0; S->spec_alpha = 1.0f; S->spec_pos = 0;
+}
+
+extern "C" int selenite_rx_set_spectrum(selenite_rx_instance *S, const selenite_rx_spec_config *sp)
+{
+    if (!S) return fail(nullptr, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_set_spectrum: S is NULL");
+    // everything is validated before anything changes: a refused call leaves the instance as it was
+    if (sp) {
+        const char *bad = nullptr;
+        int code = SELENITE_RX_ARGUMENT_ERROR;
+        if (sp->struct_size != sizeof(selenite_rx_spec_config)) bad = "struct_size is not sizeof(selenite_rx_spec_config)";
+        else if (sp->fft_len != 64 && sp->fft_len != 512) { bad = "fft_len is not 64 or 512 (the pure radix-8 lengths of arm_cfft_f32)"; code = SELENITE_RX_LENGTH_ERROR; }
+        else if (sp->stride < 1 || sp->stride > 65535) bad = "stride is not 1 .. 65535";
+        else if (sp->average > 1) bad = "average is not 0 or 1";
+        else if (!(sp->alpha > 0.0f && sp->alpha <= 1.0f)) bad = "alpha is not finite in (0, 1]";
+        else if (sp->window)
+            for (uint32_t k = 0; k < sp->fft_len && !bad; ++k)
+                if (!std::isfinite(sp->window[k])) bad = "window holds a non-finite value";
+        if (bad) {
+            g_last_error = std::string("selenite_rx_set_spectrum: ") + bad;
+            return code;
+        }
+    }
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    spec_release(S);
+    if (!sp) return SELENITE_RX_SUCCESS;
+    const size_t C = S->cfg.channels, N = sp->fft_len;
+    std::vector<float> tw(2 * N);
+    spec_twiddles(tw.data(), (uint32_t)N);
+    hipError_t e = dev_upload(&S->d_spec_tw, tw.data(), 2 * N);
+    if (e == hipSuccess && sp->window) e = dev_upload(&S->d_spec_window, sp->window, N);
+    if (e == hipSuccess) e = hipMalloc((void **)&S->d_spec_rows, C * N * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void **)&S->d_spec_pending, C * N * 2 * sizeof(float));
+    if (e != hipSuccess) {
+        spec_release(S);
+        return fail(S, SELENITE_RX_DEVICE_ERROR, std::string("selenite_rx_set_spectrum: hipMalloc: ") + hipGetErrorString(e));
+    }
+    S->spec_len = (uint32_t)N; S->spec_stride = sp->stride; S->spec_average = sp->average; S->spec_alpha = sp->alpha;
+    return spec_init_state(S);
+}
+
+// frames transformed since set_spectrum / reset: the complete frames f < pos / N with f % stride == 0
+static uint64_t spec_frames(const selenite_rx_instance *S)
+{
+    return (S->spec_pos / S->spec_len + S->spec_stride - 1) / S->spec_stride;
+}
+
+extern "C" int selenite_rx_get_spectrum(selenite_rx_instance *S, float *rows, uint64_t *frames)
+{
+    if (!S || !S->spec_len) return SELENITE_RX_ARGUMENT_ERROR;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    if (rows) HIPCHK(S, hipMemcpy(rows, S->d_spec_rows, (size_t)S->cfg.channels * S->spec_len * sizeof(float), hipMemcpyDeviceToHost));
+    if (frames) *frames = spec_frames(S);
+    return SELENITE_RX_SUCCESS;
+}
+
+extern "C" const float *selenite_rx_spectrum_device(const selenite_rx_instance *S) { return S ? S->d_spec_rows : nullptr; }
+
+static int spec_state_copy(selenite_rx_instance *S, const selenite_rx_spec_state_view *v, bool to_host)
+{
+    if (!S || !v || !S->spec_len) return SELENITE_RX_ARGUMENT_ERROR;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    const size_t n = (size_t)S->cfg.channels * S->spec_len * sizeof(float);
+    if (to_host) {
+        if (v->rows) HIPCHK(S, hipMemcpy(v->rows, S->d_spec_rows, n, hipMemcpyDeviceToHost));
+        if (v->pending) HIPCHK(S, hipMemcpy(v->pending, S->d_spec_pending, 2 * n, hipMemcpyDeviceToHost));
+        if (v->position) *v->position = S->spec_pos;
+    } else {
+        if (v->rows) HIPCHK(S, hipMemcpy(S->d_spec_rows, v->rows, n, hipMemcpyHostToDevice));
+        if (v->pending) HIPCHK(S, hipMemcpy(S->d_spec_pending, v->pending, 2 * n, hipMemcpyHostToDevice));
+        if (v->position) S->spec_pos = *v->position;
+    }
+    return SELENITE_RX_SUCCESS;
+}
+extern "C" int selenite_rx_get_spectrum_state(selenite_rx_instance *S, const selenite_rx_spec_state_view *v) { return spec_state_copy(S, v, true); }
+extern "C" int selenite_rx_set_spectrum_state(selenite_rx_instance *S, const selenite_rx_spec_state_view *v) { return spec_state_copy(S, v, false); }
+
 // ------------------------------------------------------------------------------------------
 static RxParams make_params(selenite_rx_instance *S, uint32_t block_size)
 {
@@ -1023,12 +1125,37 @@ static int out_finish(selenite_rx_instance *S, const float *audio, void *dst, bo
     return SELENITE_RX_SUCCESS;
 }
 
+// Step 0b, the spectrum tap: one launch per call on the instance's stream, on the caller's own input (f32, or int16 read directly), in
+// front of everything else.  The stream position advances by the call's length; every channel chunk of a host-pointer call starts from
+// the same one (process_host).  A call that touches no transformed frame launches nothing.
+static int spec_run(selenite_rx_instance *S, const void *src, bool src_q15, uint32_t block_size)
+{
+    const uint32_t N = S->spec_len, stride = S->spec_stride;
+    const uint64_t f0 = S->spec_pos / N;
+    SpecParams q{};
+    q.off = (uint32_t)(S->spec_pos % N);
+    q.first = (uint32_t)((stride - f0 % stride) % stride);
+    S->spec_pos += block_size;
+    if (((uint64_t)q.off + block_size - 1) / N < q.first) return SELENITE_RX_SUCCESS;      // the frames the call touches are all skipped ones
+    q.channels = S->sub_count ? S->sub_count : S->cfg.channels;
+    q.block_size = block_size; q.in_stride = block_size;
+    q.stride = stride; q.average = S->spec_average; q.alpha = S->spec_alpha;
+    q.tw = S->d_spec_tw; q.window = S->d_spec_window;
+    const size_t c0 = S->sub_count ? S->sub_first : 0;      // a channel range of the instance (make_params): the stage's arrays move with it
+    q.rows = S->d_spec_rows + c0 * N; q.pending = S->d_spec_pending + c0 * N * 2;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, launch_spectrum(q, N, src, src_q15, S->stream));
+    return SELENITE_RX_SUCCESS;
+}
+
 // With a stage the chain runs exactly as without one, into the instance's f32 audio buffer, and the stage kernel writes the caller's dst.
 // int16 slots: the fused kernels convert in and out symmetrically, so the input is converted up front (arm_q15_to_float over the whole
 // buffer, the operation the fused int16 load performs) and the call runs as an f32 call whose stage stores int16.
 static int run_chain(selenite_rx_instance *S, const void *src, bool src_q15, void *dst, bool dst_q15,
                      uint32_t block_size, Phase phase, float *ext_env)
 {
+    if (S->spec_len && phase != kPhase2)
+        if (int rc = spec_run(S, src, src_q15, block_size)) return rc;
     if (!S->out_on) return run_chain_core(S, src, src_q15, dst, dst_q15, block_size, phase, ext_env);
     if (phase != kAll) return fail(S, SELENITE_RX_ARGUMENT_ERROR, "the split global-gain calls exchange audio at the decimated rate: not with an output stage");
     HIPCHK(S, hipSetDevice(S->device));
@@ -1119,6 +1246,7 @@ extern "C" int selenite_rx_global_process_f32_device(selenite_rx_instance *S, co
     // (an output stage sits behind phase 2: both phases work on the instance's audio buffer, the stage writes dDstAudio)
     float *audio = dDstAudio;
     if (S->out_on && (rc = out_audio(S, blockSize, &audio))) return rc;
+    if (S->spec_len && (rc = spec_run(S, dSrcIQ, false, blockSize))) return rc;
     rc = run_chain_core(S, dSrcIQ, false, audio, false, blockSize, kPhase1, S->d_env);
     if (rc) return rc;
     if (rccl_comm) {                                        // NULL: single rank, nothing to exchange
@@ -1228,6 +1356,7 @@ static void process_host(selenite_rx_instance *S, const void *src, void *dst, ui
     auto &P = S->pipe;
     const uint32_t phase0 = S->phase_host;                  // the shared LO of a call is one table: every chunk starts from the same phase
     uint32_t phase_end = phase0;
+    const uint64_t spec_pos0 = S->spec_pos;                 // ... and the spectrum tap's frames from the same stream position
     const char *hs = static_cast<const char *>(src);
     char *hd = static_cast<char *>(dst);
     bool ok = true;
@@ -1254,6 +1383,7 @@ static void process_host(selenite_rx_instance *S, const void *src, void *dst, ui
         if (!ok) break;
         S->sub_first = c0; S->sub_count = n;
         S->phase_host = phase0;
+        S->spec_pos = spec_pos0;
         const int rc = run_chain(S, P.d_in[s], q15, P.d_out[s], q15, block_size, kAll, nullptr);
         phase_end = S->phase_host;
         S->sub_first = 0; S->sub_count = 0;
@@ -1266,6 +1396,7 @@ static void process_host(selenite_rx_instance *S, const void *src, void *dst, ui
         chk(hipEventRecord(P.ev_out[s], P.d2h), "event");
     }
     S->phase_host = ok ? phase_end : phase0;
+    S->spec_pos = ok ? spec_pos0 + block_size : spec_pos0;
     if (stage_out && ok) {
         if (nchunk >= 2) drain_out(nchunk - 2);
         drain_out(nchunk - 1);

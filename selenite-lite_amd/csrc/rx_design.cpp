@@ -72,3 +72,16 @@ extern "C" int selenite_rx_design_bandpass(float *coeffs, uint32_t n_stages, dou
     }
     return SELENITE_RX_SUCCESS;
 }
+
+extern "C" int selenite_rx_design_window(float *w, uint32_t n, int kind)
+{
+    if (!w || n < 2 || (kind != SELENITE_RX_WINDOW_HANN && kind != SELENITE_RX_WINDOW_BLACKMAN_HARRIS)) return SELENITE_RX_ARGUMENT_ERROR;
+    for (uint32_t i = 0; i < n; ++i) {
+        const double a = 2.0 * kPi * (double)i / (double)n;      // periodic form: the frame is one period of the transform
+        const double v = kind == SELENITE_RX_WINDOW_HANN
+                             ? 0.5 - 0.5 * std::cos(a)
+                             : 0.35875 - 0.48829 * std::cos(a) + 0.14128 * std::cos(2.0 * a) - 0.01168 * std::cos(3.0 * a);
+        w[i] = (float)v;
+    }
+    return SELENITE_RX_SUCCESS;
+}

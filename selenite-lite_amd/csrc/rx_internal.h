@@ -170,6 +170,25 @@ hipError_t launch_out(const OutParams &q, uint32_t interp, bool stereo, bool dst
 // arm_q15_to_float over n values, any n (launch_q15_to_f32 wants whole groups of eight)
 hipError_t launch_q15_to_f32_any(const int16_t *src, float *dst, size_t n, hipStream_t st);
 
+// ---- spectrum tap (rx_spectrum.hip): window -> arm_cfft_f32 -> arm_cmplx_mag_squared_f32 -> averaged, display-ordered row, on the raw input ----
+struct SpecParams {
+    uint32_t channels;     // channels of this launch (a sub-range on the host-pointer path: rows and pending are offset to it)
+    uint32_t block_size;   // input samples per channel in this call
+    uint32_t in_stride;    // complex samples between consecutive channels of the source
+    uint32_t off;          // samples of the call's first frame that arrived with earlier calls (stream position % fft_len)
+    uint32_t first;        // frames from the call's first frame to the first one that is transformed (frame index % stride == 0), < stride
+    uint32_t stride;
+    uint32_t average;      // 1: row += alpha * (p - row); 0: row = p
+    float alpha;
+    const float *tw;       // [fft_len][2] (cos, sin) (rx_api.hip: spec_twiddles)
+    const float *window;   // [fft_len] or NULL
+    float *rows;           // [C][fft_len] display order
+    float *pending;        // [C][fft_len][2] the samples so far of the frame the stream stands in
+};
+hipError_t launch_spectrum(const SpecParams &q, uint32_t fft_len, const void *src, bool src_q15, hipStream_t st);
+// host: twiddleCoef_n regenerated, tw[n][2] = (cos, sin)(2 pi i / n) as the reference's table holds them
+void spec_twiddles(float *tw, uint32_t n);
+
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
     int kind = 0;                 // 0 = none
@@ -294,6 +313,12 @@ struct selenite_rx_instance {
     uint32_t out_interp = 1, out_taps = 0, out_frames = SELENITE_RX_OUT_MONO;
     float *d_out_coeffs = nullptr, *d_out_state = nullptr;    // [out_taps] | [channels][out_taps / out_interp - 1]
     float *d_out_audio = nullptr; size_t out_audio_bytes = 0;   // f32 audio of the chain in front of the stage, [channels][blockSize / decim]
+    // spectrum tap (selenite_rx_set_spectrum): spec_len = 0: no stage, no buffers
+    uint32_t spec_len = 0, spec_stride = 1, spec_average = 0;
+    float spec_alpha = 1.0f;
+    uint64_t spec_pos = 0;             // input samples per channel since set_spectrum / reset
+    float *d_spec_tw = nullptr, *d_spec_window = nullptr;      // [spec_len][2] | [spec_len] or NULL
+    float *d_spec_rows = nullptr, *d_spec_pending = nullptr;   // [channels][spec_len] | [channels][spec_len][2]
     int status = SELENITE_RX_SUCCESS;
     std::string err;
 };

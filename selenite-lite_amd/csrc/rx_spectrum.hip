@@ -1,0 +1,256 @@
+// rx_spectrum.hip -- spectrum tap (step 0b of DESIGN.md section 2, section 5.8): per channel, on the raw input I/Q of the call in front of the
+// NCO, the power spectrum a panadapter draws.  The stream is cut into frames of N = 64 or 512 complex samples; every stride-th frame is
+//     arm_cmplx_mult_real_f32(frame, window)          ComplexMathFunctions/arm_cmplx_mult_real_f32.c (absent without a window)
+//     arm_cfft_f32(&arm_cfft_sR_f32_lenN, frame, 0, 1) TransformFunctions/arm_cfft_f32.c:562-616 = arm_radix8_butterfly_f32
+//                                                     (arm_cfft_radix8_f32.c:45-285) + the base-8 digit reversal of arm_bitreversal_32
+//     arm_cmplx_mag_squared_f32                        re * re, im * im, then the sum, each rounded
+// and the row is either that power or row + alpha * (p - row), stored display-ordered (bin k at (k + N / 2) mod N).
+//
+// Every operation of the reference is kept, in its order, and the unit is compiled with -ffp-contract=off and IEEE denormals: bit-exact in
+// every arith mode.  The reference has two butterfly forms: the j = 0 column of a pass and the whole last pass store the sums as they are
+// (:72-135), the other columns multiply them by the twiddles (:143-281).  Both compute the same sums in the same order, so one function
+// serves both and the lanes of column 0 skip the multiplies (1 * x + 0 * y is not x for Inf, NaN and the sign of zero).
+//
+// One single-wave workgroup per channel; no two wavefronts touch one channel's state.  A radix-8 pass of 512 points is 64 butterflies, one
+// per lane:
+//   pass 1  lane j owns elements j + 64 m: eight 512-byte wave loads (256 bytes for int16 slots) put them straight into registers, the window
+//           multiply and the butterfly run there -- no LDS in front of pass 1;
+//   pass 2  lane 8 g + j owns 64 g + j + 8 m: exchanged through LDS at index e + 8 (e >> 6): the eight groups of a wave would otherwise sit
+//           512 bytes apart, on the same banks;
+//   pass 3  lane b owns 8 b + m: exchanged at index e + (e >> 3) (stride 9 instead of 8 between lanes).
+// Both exchanges are conflict-free in writes and reads (64-bit accesses, 32 lanes per LDS cycle covering the 64 banks once).
+// N = 64 is passes 2 and 3 alone with eight frames per wave (lane 8 f + j owns elements j + 8 m of frame slot f; the slots are consecutive
+// TRANSFORMED frames, so a stride leaves no lane idle); their powers go through LDS to lane k = display index, which averages them in order.
+// The row lives in registers across the frames of a call: read once (averaging only) and written once per call.  The pending frame is read
+// only by a call that starts inside a transformed frame and written only by one that ends inside one; skipped frames are never read.
+#include "rx_internal.h"
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+
+namespace srx {
+
+// twiddleCoef_N (CommonTables/arm_common_tables.c) regenerated on the host, as host_sin_table() does for sinTable_f32: the source holds every
+// entry as a nine-decimal literal of cos / sin(2 pi i / N), so entry i = float("%.9f" % cos), float("%.9f" % sin) -- signs of the zeros
+// included (a tiny negative value prints as -0.000000000).  The plain (float)cos differs in 3 / 19 entries of the 64 / 512 table.
+void spec_twiddles(float *tw, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        const double a = 2.0 * 3.14159265358979323846 * (double)i / (double)n;
+        char buf[32];
+        std::snprintf(buf, sizeof buf, "%.9f", std::cos(a));
+        tw[2 * i] = std::strtof(buf, nullptr);
+        std::snprintf(buf, sizeof buf, "%.9f", std::sin(a));
+        tw[2 * i + 1] = std::strtof(buf, nullptr);
+    }
+}
+
+constexpr float kC81 = 0.70710678118f;      // arm_cfft_radix8_f32.c:62, as the reference writes it
+
+// arm_radix8_butterfly_f32's eight-point butterfly without the twiddle multiplies: a[m] = element i1 + m * n2 (:74-132 / :175-251)
+__device__ __forceinline__ void bfly8(float2 (&a)[8])
+{
+    float r1 = a[0].x + a[4].x, r5 = a[0].x - a[4].x;
+    float r2 = a[1].x + a[5].x, r6 = a[1].x - a[5].x;
+    float r3 = a[2].x + a[6].x, r7 = a[2].x - a[6].x;
+    float r4 = a[3].x + a[7].x, r8 = a[3].x - a[7].x;
+    float t1 = r1 - r3;
+    r1 = r1 + r3;
+    r3 = r2 - r4;
+    r2 = r2 + r4;
+    float s1 = a[0].y + a[4].y, s5 = a[0].y - a[4].y;
+    float s2 = a[1].y + a[5].y, s6 = a[1].y - a[5].y;
+    float s3 = a[2].y + a[6].y, s7 = a[2].y - a[6].y;
+    float s4 = a[3].y + a[7].y, s8 = a[3].y - a[7].y;
+    float t2 = s1 - s3;
+    s1 = s1 + s3;
+    s3 = s2 - s4;
+    s2 = s2 + s4;
+    a[0] = make_float2(r1 + r2, s1 + s2);
+    a[4] = make_float2(r1 - r2, s1 - s2);
+    a[2] = make_float2(t1 + s3, t2 - r3);
+    a[6] = make_float2(t1 - s3, t2 + r3);
+    const float q1 = (r6 - r8) * kC81;
+    r6 = (r6 + r8) * kC81;
+    const float q2 = (s6 - s8) * kC81;
+    s6 = (s6 + s8) * kC81;
+    t1 = r5 - q1;
+    r5 = r5 + q1;
+    r8 = r7 - r6;
+    r7 = r7 + r6;
+    t2 = s5 - q2;
+    s5 = s5 + q2;
+    s8 = s7 - s6;
+    s7 = s7 + s6;
+    a[1] = make_float2(r5 + s7, s5 - r7);
+    a[7] = make_float2(r5 - s7, s5 + r7);
+    a[5] = make_float2(t1 + s8, t2 - r8);
+    a[3] = make_float2(t1 - s8, t2 + r8);
+}
+
+// the twiddled form's tail (:214-275): element m times (co, si) of index m * id -- p1 = co * r, p2 = si * s, p3 = co * s, p4 = si * r
+__device__ __forceinline__ void twiddle7(float2 (&a)[8], const float2 (&w)[7])
+{
+#pragma unroll
+    for (int m = 1; m < 8; ++m) {
+        const float p1 = w[m - 1].x * a[m].x, p2 = w[m - 1].y * a[m].y;
+        const float p3 = w[m - 1].x * a[m].y, p4 = w[m - 1].y * a[m].x;
+        a[m] = make_float2(p1 + p2, p3 - p4);
+    }
+}
+
+__device__ __forceinline__ float2 spec_load(const float *x, int64_t v) { return reinterpret_cast<const float2 *>(x)[v]; }
+__device__ __forceinline__ float2 spec_load(const int16_t *x, int64_t v)
+{
+    const short2 s = reinterpret_cast<const short2 *>(x)[v];
+    return make_float2(q15_to_float(s.x), q15_to_float(s.y));      // arm_q15_to_float
+}
+
+template <int N, typename TIn>
+__global__ __launch_bounds__(64) void k_spectrum(SpecParams q, const TIn *__restrict__ src)
+{
+    constexpr uint32_t NF = N == 512 ? 1u : 8u;              // frames per trip of the wave
+    __shared__ float2 fs[576];                               // 512 elements + the padding of either exchange (N = 64: 8 rows of 72 powers)
+
+    const uint32_t lane = threadIdx.x, c = blockIdx.x, j2 = lane & 7u, g = lane >> 3;
+    const TIn *x = src + (size_t)c * q.in_stride * 2;
+    float *pend = q.pending + (size_t)c * N * 2;
+    float *row = q.rows + (size_t)c * N;
+    // the call's samples are v = 0 .. L - 1; the samples of its first frame that came with earlier calls are v = -off .. -1, in pending[0 .. off)
+    const int64_t off = q.off, L = q.block_size;
+    const uint32_t nfr = (uint32_t)((off + L) / N);          // frames this call completes: i = 0 .. nfr - 1, frame i starts at v = i * N - off
+    // the transformed ones are i = first + t * stride, t < ne
+    const uint32_t ne = nfr > q.first ? (nfr - 1u - q.first) / q.stride + 1u : 0u;
+    auto elem = [&](int64_t v) -> float2 {
+        if (v < 0) return reinterpret_cast<const float2 *>(pend)[v + off];
+        return spec_load(x, v);
+    };
+
+    if (ne) {
+        // lane's elements in the load layout, its window values and twiddles
+        const uint32_t e0 = N == 512 ? lane : j2, es = N == 512 ? 64u : 8u;
+        float w[8];
+        float2 tw1[7], tw2[7];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) w[m] = q.window ? q.window[e0 + es * m] : 1.0f;
+#pragma unroll
+        for (int k = 1; k < 8; ++k) {
+            // pass n2 = 64 (twidCoefModifier 1): ia_k = k * j; pass n2 = 8 (modifier N / 64): ia_k = k * j * N / 64 (:146-168)
+            if (N == 512) tw1[k - 1] = reinterpret_cast<const float2 *>(q.tw)[k * lane];
+            tw2[k - 1] = reinterpret_cast<const float2 *>(q.tw)[(N / 64) * k * j2];
+        }
+        // display index of power m of this lane: N = 512: position 8 * lane + m = digits (g, j2, m) holds bin 64 m + 8 j2 + g;
+        // N = 64: position 8 * j2 + m of the lane's frame holds bin 8 m + j2 (arm_bitreversal_32 with armBitRevIndexTableN: base-8 digit reversal)
+        const uint32_t dlo = N == 512 ? 8u * j2 + g : j2, dst = N == 512 ? 64u : 8u;
+        float r[8];
+        float r64 = 0.0f;
+        if (q.average) {
+            if (N == 512) {
+#pragma unroll
+                for (int m = 0; m < 8; ++m) r[m] = row[dst * ((m + 4) & 7) + dlo];
+            } else {
+                r64 = row[lane];
+            }
+        }
+
+        for (uint32_t t0 = q.average ? 0u : ne - 1u; t0 < ne; t0 += NF) {      // (no averaging: the row is the last transformed frame's power)
+            const uint32_t t = t0 + (N == 512 ? 0u : g);
+            const bool have = t < ne;
+            const int64_t v0 = (int64_t)(q.first + (uint64_t)t * q.stride) * N - off;
+            float2 a[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) a[m] = have ? elem(v0 + e0 + es * m) : make_float2(0.0f, 0.0f);
+            if (q.window) {
+#pragma unroll
+                for (int m = 0; m < 8; ++m) a[m] = make_float2(a[m].x * w[m], a[m].y * w[m]);
+            }
+            if (N == 512) {
+                bfly8(a);
+                if (lane != 0u) twiddle7(a, tw1);
+                __syncthreads();                             // (one wave: orders the LDS traffic across lanes for the compiler)
+#pragma unroll
+                for (int m = 0; m < 8; ++m) fs[lane + 72u * m] = a[m];
+                __syncthreads();
+#pragma unroll
+                for (int m = 0; m < 8; ++m) a[m] = fs[72u * g + j2 + 8u * m];
+            }
+            bfly8(a);
+            if (j2 != 0u) twiddle7(a, tw2);
+            __syncthreads();
+#pragma unroll
+            for (int m = 0; m < 8; ++m) fs[72u * g + j2 + 9u * m] = a[m];
+            __syncthreads();
+#pragma unroll
+            for (int m = 0; m < 8; ++m) a[m] = fs[9u * lane + m];
+            bfly8(a);                                        // n2 = 1: every butterfly is of the twiddle-free form
+
+            float p[8];
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const float re2 = a[m].x * a[m].x, im2 = a[m].y * a[m].y;
+                p[m] = re2 + im2;
+            }
+            if (N == 512) {
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    if (q.average) {
+                        const float d = p[m] - r[m], s = q.alpha * d;
+                        r[m] = r[m] + s;
+                    } else {
+                        r[m] = p[m];
+                    }
+                }
+            } else {
+                float *ps = reinterpret_cast<float *>(fs);
+                __syncthreads();
+#pragma unroll
+                for (int m = 0; m < 8; ++m) ps[72u * g + 8u * ((m + 4) & 7) + j2] = p[m];
+                __syncthreads();
+                for (uint32_t f = 0; f < 8u && t0 + f < ne; ++f) {
+                    const float pk = ps[72u * f + lane];
+                    if (q.average) {
+                        const float d = pk - r64, s = q.alpha * d;
+                        r64 = r64 + s;
+                    } else {
+                        r64 = pk;
+                    }
+                }
+            }
+        }
+        if (N == 512) {
+#pragma unroll
+            for (int m = 0; m < 8; ++m) row[dst * ((m + 4) & 7) + dlo] = r[m];
+        } else {
+            row[lane] = r64;
+        }
+    }
+
+    // the frame the call ends in, when it will be transformed: its samples so far wait in pending (those of earlier calls stay where they are)
+    const int64_t vt = (int64_t)nfr * N - off;
+    if (vt < L && nfr >= q.first && (nfr - q.first) % q.stride == 0u)
+        for (int64_t v = (vt > 0 ? vt : 0) + lane; v < L; v += kWave) reinterpret_cast<float2 *>(pend)[v - vt] = spec_load(x, v);
+}
+
+hipError_t launch_spectrum(const SpecParams &q, uint32_t fft_len, const void *src, bool src_q15, hipStream_t st)
+{
+    if (q.channels == 0 || q.block_size == 0) return hipSuccess;
+    if (q.stride == 0 || q.off >= fft_len) return hipErrorInvalidValue;
+    const dim3 grid(q.channels), blk(kWave);
+    if (fft_len == 512 && !src_q15) hipLaunchKernelGGL((k_spectrum<512, float>), grid, blk, 0, st, q, static_cast<const float *>(src));
+    else if (fft_len == 512) hipLaunchKernelGGL((k_spectrum<512, int16_t>), grid, blk, 0, st, q, static_cast<const int16_t *>(src));
+    else if (fft_len == 64 && !src_q15) hipLaunchKernelGGL((k_spectrum<64, float>), grid, blk, 0, st, q, static_cast<const float *>(src));
+    else if (fft_len == 64) hipLaunchKernelGGL((k_spectrum<64, int16_t>), grid, blk, 0, st, q, static_cast<const int16_t *>(src));
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+}  // namespace srx
+
+extern "C" int selenite_rx_spectrum_twiddles(float *tw, uint32_t fft_len)
+{
+    if (!tw) return SELENITE_RX_ARGUMENT_ERROR;
+    if (fft_len != 64 && fft_len != 512) return SELENITE_RX_LENGTH_ERROR;
+    srx::spec_twiddles(tw, fft_len);
+    return SELENITE_RX_SUCCESS;
+}

@@ -23,10 +23,12 @@ OPT_FORCE_GENERIC, OPT_NO_SHARED_LO, OPT_NO_PERIODIC_LO, OPT_RERUN_GRID, OPT_TX_
 SUCCESS, ARGUMENT_ERROR, LENGTH_ERROR, NANINF, DEVICE_ERROR = 0, -1, -2, -4, -7
 NR_OFF, NR_DENOISE, NR_NOTCH = 0, 1, 2                         # selenite_rx_set_nr: the NLMS stage's kind
 OUT_MONO, OUT_STEREO = 0, 1                                    # selenite_rx_set_out: the output stage's frame format
+WINDOW_HANN, WINDOW_BLACKMAN_HARRIS = 0, 1                     # selenite_rx_design_window
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
 i16p = C.POINTER(C.c_int16)
+u64p = C.POINTER(C.c_uint64)
 
 
 class Config(C.Structure):
@@ -69,6 +71,17 @@ class OutConfig(C.Structure):
                 ("coeffs", f32p)]
 
 
+class SpecConfig(C.Structure):
+    """struct selenite_rx_spec_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("fft_len", C.c_uint32), ("stride", C.c_uint32), ("average", C.c_uint32),
+                ("alpha", C.c_float), ("window", f32p)]
+
+
+class SpecStateView(C.Structure):
+    """struct selenite_rx_spec_state_view."""
+    _fields_ = [("rows", f32p), ("pending", f32p), ("position", u64p)]
+
+
 # every symbol include/selenite_rx.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "selenite_rx_init", "selenite_rx_free", "selenite_rx_set_mode", "selenite_rx_status",
@@ -88,6 +101,8 @@ ABI_SYMBOLS = [
     "selenite_rx_set_guard_ratio", "selenite_rx_guard_stats", "selenite_rx_guard_channels", "selenite_rx_auto_words", "selenite_rx_guard_handover", "selenite_rx_set_handover_repair", "selenite_rx_set_auto_launches", "selenite_rx_auto_launches_last", "selenite_rx_guard_clear",
     "selenite_rx_set_nr", "selenite_rx_get_nr_state", "selenite_rx_set_nr_state",
     "selenite_rx_set_out", "selenite_rx_out_values", "selenite_rx_get_out_state", "selenite_rx_set_out_state", "selenite_rx_design_interp",
+    "selenite_rx_set_spectrum", "selenite_rx_get_spectrum", "selenite_rx_spectrum_device", "selenite_rx_get_spectrum_state",
+    "selenite_rx_set_spectrum_state", "selenite_rx_spectrum_twiddles", "selenite_rx_design_window",
 ]
 
 class TxConfig(C.Structure):
@@ -215,6 +230,15 @@ def lib():
             L.selenite_rx_get_out_state.argtypes = [vp, f32p]
             L.selenite_rx_set_out_state.argtypes = [vp, f32p]
             L.selenite_rx_design_interp.argtypes = [f32p, C.c_uint32, C.c_uint32, C.c_double]
+        if hasattr(L, "selenite_rx_set_spectrum"):          # (an older build named by SELENITE_RX_LIB lacks the spectrum tap)
+            L.selenite_rx_set_spectrum.argtypes = [vp, C.POINTER(SpecConfig)]
+            L.selenite_rx_get_spectrum.argtypes = [vp, f32p, u64p]
+            L.selenite_rx_spectrum_device.argtypes = [vp]
+            L.selenite_rx_spectrum_device.restype = vp
+            L.selenite_rx_get_spectrum_state.argtypes = [vp, C.POINTER(SpecStateView)]
+            L.selenite_rx_set_spectrum_state.argtypes = [vp, C.POINTER(SpecStateView)]
+            L.selenite_rx_spectrum_twiddles.argtypes = [f32p, C.c_uint32]
+            L.selenite_rx_design_window.argtypes = [f32p, C.c_uint32, C.c_int]
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -247,6 +271,24 @@ def design_interp(ni_taps, interp, cutoff):
     if rc:
         raise ValueError("selenite_rx_design_interp: %d" % rc)
     return h
+
+
+def design_window(n, kind=WINDOW_HANN):
+    """a window for the spectrum tap (WINDOW_HANN / WINDOW_BLACKMAN_HARRIS), periodic form"""
+    w = np.empty(n, np.float32)
+    rc = lib().selenite_rx_design_window(_fp(w), n, kind)
+    if rc:
+        raise ValueError("selenite_rx_design_window: %d" % rc)
+    return w
+
+
+def spectrum_twiddles(fft_len):
+    """[fft_len][2] (cos, sin): the twiddle table the spectrum kernel uses (host only, no device)"""
+    tw = np.empty((fft_len, 2), np.float32)
+    rc = lib().selenite_rx_spectrum_twiddles(_fp(tw), fft_len)
+    if rc:
+        raise ValueError("selenite_rx_spectrum_twiddles: %d" % rc)
+    return tw
 
 
 def design_hilbert(num_taps):
@@ -665,6 +707,68 @@ class Rx:
         rc = self.L.selenite_rx_set_out_state(self.h, _fp(a))
         if rc:
             raise RxError(rc, "selenite_rx_set_out_state")
+
+    # -- spectrum tap (selenite_rx_set_spectrum) ------------------------------------------------
+    def set_spectrum(self, fft_len=512, stride=1, average=0, alpha=1.0, window=None):
+        """Put the spectrum tap on the raw input of every channel, or remove it (fft_len=None).  Clears the tap's state.  Raises RxError on a
+        bad field; the instance is then left as it was."""
+        old, self._spec = getattr(self, "_spec", None), None
+        if fft_len is None:
+            rc = self.L.selenite_rx_set_spectrum(self.h, None)
+        else:
+            g = SpecConfig()
+            g.struct_size = C.sizeof(SpecConfig)
+            g.fft_len, g.stride, g.average, g.alpha = int(fft_len), int(stride), int(average), float(alpha)
+            w = None
+            if window is not None:
+                w = np.ascontiguousarray(window, np.float32)
+                assert w.shape == (int(fft_len),), w.shape
+                g.window = _fp(w)
+            rc = self.L.selenite_rx_set_spectrum(self.h, C.byref(g))
+        if rc in (ARGUMENT_ERROR, LENGTH_ERROR):
+            self._spec = old
+        if rc:
+            raise RxError(rc, self.L.selenite_rx_error_string(None).decode() if rc in (ARGUMENT_ERROR, LENGTH_ERROR) else self.error())
+        self._spec = int(fft_len) if fft_len is not None else None
+
+    def _spec_len(self):
+        if getattr(self, "_spec", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the spectrum tap is off")
+        return self._spec
+
+    def spectrum(self):
+        """(rows [channels][fft_len] display order, frames transformed so far); drains the stream"""
+        rows = np.zeros((self.cfg.channels, self._spec_len()), np.float32)
+        n = C.c_uint64(0)
+        rc = self.L.selenite_rx_get_spectrum(self.h, _fp(rows), C.byref(n))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_spectrum")
+        return rows, int(n.value)
+
+    def spectrum_device(self):
+        """device address of the row buffer (None while the tap is off)"""
+        return self.L.selenite_rx_spectrum_device(self.h)
+
+    def spectrum_state(self):
+        n, c = self._spec_len(), self.cfg.channels
+        a = dict(rows=np.zeros((c, n), np.float32), pending=np.zeros((c, n, 2), np.float32), position=np.zeros(1, np.uint64))
+        v = SpecStateView(_fp(a["rows"]), _fp(a["pending"]), a["position"].ctypes.data_as(u64p))
+        rc = self.L.selenite_rx_get_spectrum_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_spectrum_state")
+        return a
+
+    def set_spectrum_state(self, d):
+        n, c = self._spec_len(), self.cfg.channels
+        shapes = dict(rows=(c, n), pending=(c, n, 2), position=(1,))
+        a = {k: np.ascontiguousarray(d[k], np.uint64 if k == "position" else np.float32) for k in d}
+        for k in a:
+            assert a[k].shape == shapes[k], (k, a[k].shape)
+        v = SpecStateView(_fp(a["rows"]) if "rows" in a else None, _fp(a["pending"]) if "pending" in a else None,
+                          a["position"].ctypes.data_as(u64p) if "position" in a else None)
+        rc = self.L.selenite_rx_set_spectrum_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_set_spectrum_state")
 
     def close(self):
         if self.h:
