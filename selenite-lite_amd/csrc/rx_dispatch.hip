@@ -1,0 +1,369 @@
+// rx_dispatch.hip -- the one dispatcher behind every process entry point: which kernels serve a call, over which channels
+// (ChanRange), from which stream positions (CallStart).  The three stages hook in here and nowhere else: the spectrum tap in front
+// of the chain, NLMS in front of the AGC, the output stage behind the chain.
+#include "rx_host.h"
+
+#include <dlfcn.h>
+
+using namespace srx;
+
+// the shared LO repeats every 256 samples and the kernel of this instance can keep it in registers
+static bool periodic_lo(const selenite_rx_instance *S)
+{
+    const selenite_rx_config &g = S->cfg;
+    if (!(g.nco_enable && S->steps_uniform && (S->h_step[0] & 0x00FFFFFFu) == 0 && !S->no_periodic_lo)) return false;
+    if ((g.arith == SELENITE_ARITH_SPLIT16 || g.arith == SELENITE_ARITH_AUTO) && S->plan.d_btab16 && g.nd_taps)
+        return 256u % (g.block / g.decim) == 0 && ssb_split16_periodic_lo(split16_template_nd((int)g.nd_taps, (int)g.decim, (int)g.nh_taps), (int)g.decim, (int)g.nh_taps);
+    if (g.arith == SELENITE_ARITH_AUTO) return false;      // (runs the bit-exact k_ssb_fused)
+    // k_ssb_mfma (fma arithmetic, and split16 shapes without a matrix kernel of their own): decimation by 4, 1024-sample passes
+    return g.arith != SELENITE_ARITH_CMSIS && S->plan.use_mfma && g.nd_taps && g.decim == 4;
+}
+
+// every channel has its own LO, each of them periodic in 256 samples (all steps multiples of 2^24), and the kernel that serves
+// this instance's whole-pass calls computes one period per channel and call and keeps it in registers (NCO == 4 flavour of
+// k_ssb_split16 and of k_ssb_fused; k_ssb_mfma and k_hilb_split16 have none: per-sample NCO there)
+static bool periodic_lo_per_channel(const selenite_rx_instance *S)
+{
+    const selenite_rx_config &g = S->cfg;
+    if (!(g.nco_enable && S->steps_grid256 && !S->no_periodic_lo && S->plan.kind != 0)) return false;
+    if (256u % (g.block / g.decim) != 0) return false;                       // passes of 256 outputs only
+    const bool split = (g.arith == SELENITE_ARITH_SPLIT16 || g.arith == SELENITE_ARITH_AUTO) && S->plan.d_btab16;
+    if (split && g.nd_taps) return ssb_split16_periodic_lo(split16_template_nd((int)g.nd_taps, (int)g.decim, (int)g.nh_taps), (int)g.decim, (int)g.nh_taps);
+    if (split) return false;                                                 // k_hilb_split16: per-sample NCO (and its AUTO rerun with it)
+    const bool exact = g.arith == SELENITE_ARITH_CMSIS || g.arith == SELENITE_ARITH_AUTO;
+    return exact || !(S->plan.use_mfma && g.decim == 4);                     // k_ssb_fused; the fma arithmetic by 4 runs k_ssb_mfma
+}
+
+extern "C" const char *selenite_rx_nco_path(const selenite_rx_instance *S)
+{
+    if (!S) return "";
+    if (!S->cfg.nco_enable) return "off";
+    const bool fused = !S->force_generic && (S->plan.kind != 0 || cw_fused_ok(S->cfg, S->cfg.block));
+    if (!fused || !S->steps_uniform || !S->phase_uniform || S->no_shared_lo) {
+        if (fused && S->plan.kind != 0 && periodic_lo_per_channel(S))
+            return "per-channel LO, period 256 samples (arm_sin/cos_f32 once per channel and call), held in registers";
+        return "per-channel arm_sin/cos_f32 in the kernel";
+    }
+    return periodic_lo(S) ? "shared LO, period 256 samples, held in registers" : "shared LO table per call";
+}
+
+// SELENITE_ARITH_AUTO on a shape with a split-precision decimator: the rows k_ssb_split16 leaves for k_hist_exact, allocated by the
+// first call that can use them
+static int ensure_hist_ext(selenite_rx_instance *S)
+{
+    if (S->d_hist_ext || !S->ext_len || !S->handover_repair || !S->d_rerun_flag) return SELENITE_RX_SUCCESS;
+    const size_t n = 2 * (size_t)S->cfg.channels * S->ext_len;
+    HIPCHK(S, hipMalloc((void **)&S->d_hist_ext, n * sizeof(float2)));
+    HIPCHK(S, hipMemsetAsync(S->d_hist_ext, 0, n * sizeof(float2), S->stream));
+    return SELENITE_RX_SUCCESS;
+}
+
+// ------------------------------------------------------------------------------------------
+RxParams srx::make_params(selenite_rx_instance *S, ChanRange r, uint32_t block_size)
+{
+    const selenite_rx_config &g = S->cfg;
+    RxParams p{};
+    p.channels = r.count; p.block = g.block; p.decim = g.decim;
+    p.nd = g.nd_taps; p.nh = g.nh_taps; p.nbiq = g.n_biquad; p.mode = g.mode; p.q15_round = g.q15_rounding ? 1u : 0u;
+    p.nco = g.nco_enable ? 1 : 0; p.agc = g.agc_enable ? 1 : 0;
+    p.block_size = block_size; p.nout = block_size / g.decim;
+    p.in_stride = p.block_size; p.out_stride = p.nout;
+    p.dec_c = S->d_dec_c; p.hilb_c = S->d_hilb_c; p.delay_c = S->d_delay_c; p.biq_c = S->d_biq_c;
+    p.sintab = S->d_sintab; p.step = S->d_step; p.phase = S->d_phase;
+    p.dec_state = S->d_dec_state; p.fir_state = S->d_fir_state; p.biq_state = S->d_biq_state;
+    p.gain = S->d_gain;
+    p.flags = S->d_flags;
+    p.guard_ratio = S->guard_ratio;
+    p.guard_ch = S->d_guard_ch;
+    p.guard_calls = S->d_guard_ch + g.channels;
+    p.guard_hand = S->d_guard_ch + 2 * (size_t)g.channels;
+    p.hist_ext = S->handover_repair ? S->d_hist_ext : nullptr; p.ext_len = S->ext_len; p.ext_buf_stride = (size_t)g.channels * S->ext_len;
+    const size_t c0 = r.first;                              // every per-channel array moves with the range
+    p.step += c0; p.phase += c0; p.gain += c0; p.guard_ch += c0; p.guard_calls += c0; p.guard_hand += c0;
+    if (p.hist_ext) p.hist_ext += c0 * p.ext_len;
+    if (p.dec_state) p.dec_state += c0 * 2 * (g.nd_taps - 1);
+    if (p.fir_state) p.fir_state += c0 * 2 * (g.nh_taps - 1);
+    if (p.biq_state) p.biq_state += c0 * 4 * g.n_biquad;
+    p.agcp = AgcParams{ g.agc_target, g.agc_attack, g.agc_decay, g.agc_gain_min, g.agc_gain_max, g.agc_env_floor };
+    // generic front kernel: largest pass (<= 256 outputs) whose LDS image fits 64 KiB
+    uint32_t P = 256;
+    for (;;) {
+        p.pass_out = P;
+        if (front_generic_lds_bytes(p) <= 64 * 1024 || P == 1) break;
+        P >>= 1;
+    }
+    return p;
+}
+
+bool srx::block_size_ok(selenite_rx_instance *S, uint32_t block_size, const char *who)
+{
+    if (block_size == 0 || block_size % S->cfg.block != 0) {
+        fail(S, SELENITE_RX_LENGTH_ERROR, std::string(who) + ": blockSize is not a non-zero multiple of cfg.block");
+        return false;
+    }
+    return true;
+}
+
+// The one dispatcher behind every process entry point.
+// (phase_now: the common NCO phase at the first sample of this launch)
+static int run_part(selenite_rx_instance *S, ChanRange r, uint32_t phase_now, const void *src, bool src_q15, void *dst, bool dst_q15,
+                    uint32_t block_size, Phase phase, float *ext_env, uint32_t in_stride, uint32_t out_stride)
+{
+    const selenite_rx_config &g = S->cfg;
+    HIPCHK(S, hipSetDevice(S->device));
+    if (phase != kPhase2 && S->plan.kind != 0 && S->plan.d_btab16 && !S->force_generic)
+        if (int rc = ensure_hist_ext(S)) return rc;
+    RxParams p = make_params(S, r, block_size);
+    p.in_stride = in_stride; p.out_stride = out_stride;
+    if (front_generic_lds_bytes(p) > 64 * 1024 && (S->force_generic || S->plan.kind == 0))
+        return fail(S, SELENITE_RX_LENGTH_ERROR, "filter lengths exceed the LDS budget of the generic kernel");
+    const int arith = (int)g.arith;
+    const int garith = arith == SELENITE_ARITH_AUTO ? SELENITE_ARITH_CMSIS : arith;      // the generic kernels: AUTO is bit-exact there
+    const bool global = g.agc_enable && g.agc_global;
+    const bool cw = mode_is_cw(g.mode) && g.n_biquad;
+    const bool nr = phase != kPhase2 && S->nr.kind != SELENITE_RX_NR_OFF;      // NLMS stage in front of the AGC (rx_nlms.hip)
+    hipStream_t st = S->stream;
+
+    // Fused kernels serve the global-gain variant too: they run with their own AGC off (un-scaled
+    // audio out), then the envelope reduction and the gain pass below finish the call.
+    // (the fused kernels convert in and out symmetrically, and a global gain needs f32 audio between its two phases: int16 slots with
+    // a global gain get their input converted once, up front -- arm_q15_to_float over the whole buffer, the very operation the fused
+    // int16 load performs -- and run as an f32-input call whose gain pass stores int16; round 2 left them to the generic kernels)
+    // (the NLMS stage the same way: the fused kernel leaves un-scaled f32 audio, the stage runs in place on it, the AGC pass stores)
+    const bool fusable = phase != kPhase2 && !S->force_generic;
+    const bool ssb_fused = fusable && S->plan.kind != 0;
+    const bool cw_fused = fusable && cw_fused_ok(g, block_size) && cw_strides_ok(p.in_stride, p.out_stride);    // (wider strides: the generic kernels)
+    if ((global || nr) && src_q15 && (ssb_fused || cw_fused)) {
+        // int16 values of the call (block_size % 4 == 0 for every fused shape), up to the end of the last channel's block_size samples: the
+        // second part of a fused_tail_split call starts inside the rows (= p.channels * p.in_stride * 2 when the call is not split)
+        const size_t nval = ((size_t)(p.channels - 1) * p.in_stride + block_size) * 2;
+        if (nval % 8 == 0) {
+            int rc = ensure(S, (void **)&S->d_conv_in, &S->conv_in_bytes, nval * sizeof(float));
+            if (rc) return rc;
+            HIPCHK(S, launch_q15_to_f32(static_cast<const int16_t *>(src), S->d_conv_in, nval, S->stream));
+            src = S->d_conv_in;
+            src_q15 = false;
+        }
+    }
+    float *audio = (float *)dst;      // un-scaled audio: dst itself when dst is f32, else scratch
+    if (dst_q15 && (global || nr || !(ssb_fused || cw_fused))) {
+        const size_t need = (size_t)g.channels * p.out_stride * sizeof(float);
+        int rc = ensure(S, (void **)&S->d_scratch, &S->scratch_bytes, need);
+        if (rc) return rc;
+        audio = S->d_scratch;
+    }
+    // (SELENITE_ARITH_AUTO outside the SSB fused kernels -- CW, generic: every channel's state stays in exact arithmetic, and the
+    // provenance words k_ssb_split16 reads at its next call say so)
+    // (a channel the matrix kernel left with its samples gets its Hilbert-pair history recomputed in exact arithmetic first: the
+    // generic / CW kernels read it -- advisor finding, round 3)
+    if (phase != kPhase2 && S->d_rerun_flag && !ssb_fused) {
+        uint32_t *words = S->d_rerun_flag + r.first;
+        if (p.hist_ext) {
+            RxParams ph = p;
+            ph.chan_flags = words;
+            HIPCHK(S, launch_hist_exact(ph, true, st));
+        }
+        HIPCHK(S, hipMemsetAsync(words, 0, p.channels * sizeof(uint32_t), st));
+    }
+    bool env_emitted = false;      // global gain: the fused kernel wrote the per-channel block maxima
+    if (ssb_fused || cw_fused) {
+        RxParams pf = p;
+        if (g.nco_enable && S->steps_uniform && S->phase_uniform && !S->no_shared_lo) {
+            // one LO for all channels: computed once per call, read from L2 by every wavefront
+            // the table is a pure function of (start phase, step, length): a call that starts where the table in d_lo
+            // starts reuses it -- every chunk of a pipelined host call, and EVERY call when the phase advance of a call
+            // is a multiple of 2^32 (an LO on the fs / 256 grid with calls of whole DSP blocks)
+            // (at least one whole period: the register-resident flavour reads LO[0 .. 255] whatever the call length)
+            const uint32_t lo_n = block_size < 256u ? 256u : block_size;
+            if (!(S->lo_valid && S->lo_phase == phase_now && S->lo_step == S->h_step[0] && S->lo_n >= lo_n)) {
+                S->lo_valid = false;
+                int rc = ensure(S, (void **)&S->d_lo, &S->lo_bytes, (size_t)lo_n * sizeof(float2));
+                if (rc) return rc;
+                HIPCHK(S, launch_lo_table(S->d_lo, S->d_sintab, phase_now, S->h_step[0], lo_n, st));
+                S->lo_valid = true; S->lo_phase = phase_now; S->lo_step = S->h_step[0]; S->lo_n = lo_n;
+            }
+            pf.nco = 2;
+            pf.lo = S->d_lo;
+            // a step that is a multiple of 2^24 repeats the LO every 256 samples (channelised receivers: LO
+            // frequencies on a grid of fs / 256): k_ssb_split16 then keeps it in registers (its NCO == 3 flavour)
+            pf.lo_period = periodic_lo(S) ? 256u : 0u;
+        } else if (ssb_fused && g.nco_enable && periodic_lo_per_channel(S)) {
+            pf.lo_period = 256u;                          // pf.nco stays 1: every channel computes its own period once
+        }
+        if (arith == SELENITE_ARITH_AUTO && ssb_fused) {
+            // the split16 kernel raises the rerun flag of the channels it guards and leaves their state alone; the bit-exact
+            // kernel then recomputes the flagged channels (launch_fused)
+            pf.rerun_flag = S->d_rerun_flag + r.first;
+            pf.chan_list = S->d_rerun_list + 2;
+            pf.chan_count = S->d_rerun_list;              // the two counters; launch_shape picks by *rerun_par_host where it launches the prepare kernel
+            pf.rerun_par_host = &S->rerun_par;
+            pf.rerun_seen = S->h_rerun_seen;
+            pf.auto_inline = S->auto_launches == 1 ? 1u : 0u;
+            pf.form_host = &S->auto_form_last;
+        }
+        void *fdst = dst;
+        bool fq15 = dst_q15;
+        if (global || nr) {
+            pf.agc = 0; fdst = audio; fq15 = false;
+            pf.out_cached = 1;                            // phase 2 (and, without block maxima from the kernel, the envelope fold) reads this audio back
+            // k_ssb_split16 (16-lane DSP blocks, whole passes) leaves the block maxima of every channel behind: the
+            // envelope reduction below then folds channels x blocks floats instead of reading the audio again
+            if (!nr && ssb_fused && (arith == SELENITE_ARITH_SPLIT16 || arith == SELENITE_ARITH_AUTO) && S->plan.d_btab16 && g.nd_taps && g.decim == 4 && (g.block / g.decim) / 4 == 16 &&
+                (block_size / g.decim) % 256 == 0 && g.nco_enable && g.mode != SELENITE_MODE_AM && g.mode != SELENITE_MODE_FM) {   // the launches with the DPP block reductions (decimation by 4, 64-sample audio blocks)
+                const size_t need = sizeof(float) * env_fold_scratch_floats(p.channels, block_size / g.block);
+                int rc = ensure(S, (void **)&S->d_env_part, &S->env_part_cap, need);
+                if (rc) return rc;
+                pf.env_part = S->d_env_part;
+                env_emitted = true;
+            }
+        }
+        if (ssb_fused) HIPCHK(S, launch_fused(S->plan, pf, arith, src, src_q15, fdst, fq15, S->delay_index, st));
+        else HIPCHK(S, launch_cw_fused(pf, src, src_q15, fdst, fq15, st));
+        if (!global && !nr) return SELENITE_RX_SUCCESS;
+    }
+
+    // generic path: front -> [biquad] -> AGC / convert
+    if (phase != kPhase2 && !(ssb_fused || cw_fused)) {
+        HIPCHK(S, launch_front_generic(p, garith, src, src_q15, audio, st));
+        if (cw) HIPCHK(S, launch_biquad_generic(p, garith, audio, st));
+    }
+    // step 4b: NLMS in place on the un-scaled audio (phase 1 of a global gain: before the envelope)
+    if (nr) HIPCHK(S, launch_nlms(S->nr.params(r, p), S->nr.taps, audio, st));
+    if (global) {
+        float *env = ext_env;
+        if (!env) {
+            const size_t need = sizeof(float) * (block_size / g.block);
+            int rc = ensure(S, (void **)&S->d_env, &S->env_cap, need);
+            if (rc) return rc;
+            env = S->d_env;
+        }
+        if (phase != kPhase2) {
+            if (env_emitted) {
+                HIPCHK(S, launch_env_fold(S->d_env_part, env, p.channels, block_size / g.block, st));
+            } else {
+                const size_t need = sizeof(float) * env_global_rows(p) * (block_size / g.block);
+                int rc = ensure(S, (void **)&S->d_env_part, &S->env_part_cap, need);
+                if (rc) return rc;
+                HIPCHK(S, launch_env_global(p, audio, S->d_env_part, env, st));
+            }
+        }
+        if (phase != kPhase1) HIPCHK(S, launch_agc_apply_global(p, garith, audio, env, dst, dst_q15, st));
+    } else if (g.agc_enable || dst_q15) {
+        HIPCHK(S, launch_agc_generic(p, garith, audio, dst, dst_q15, st));
+    }
+    return SELENITE_RX_SUCCESS;
+}
+
+// Entry of every process call.  Any call length (a whole number of DSP blocks) runs on the fused kernels; a
+// split-precision call that ends in a partial pass too short for the matrix kernel is cut in two launches on the same
+// streaming state (fused_tail_split; both parts address the caller's buffers with the full per-channel stride; in
+// SELENITE_ARITH_AUTO the tail runs in the bit-exact arithmetic, rx_fused.hip launch_shape).
+static int run_chain_core(selenite_rx_instance *S, ChanRange r, uint32_t phase_now, const void *src, bool src_q15, void *dst, bool dst_q15,
+                          uint32_t block_size, Phase phase, float *ext_env)
+{
+    const selenite_rx_config &g = S->cfg;
+    const uint32_t nout = block_size / g.decim;
+    const bool global = g.agc_enable && g.agc_global;
+    if (phase == kAll && !global && !S->force_generic && S->plan.kind != 0 && fused_tail_split(S->plan, g, block_size)) {
+        const uint32_t unit = split16_pass_out(g.block, g.decim) * g.decim, bs1 = block_size / unit * unit;
+        {
+            int rc = run_part(S, r, phase_now, src, src_q15, dst, dst_q15, bs1, kAll, nullptr, block_size, nout);
+            if (rc) return rc;
+            const size_t ein = src_q15 ? sizeof(int16_t) : sizeof(float), eout = dst_q15 ? sizeof(int16_t) : sizeof(float);
+            const char *src2 = static_cast<const char *>(src) + (size_t)bs1 * 2 * ein;
+            char *dst2 = static_cast<char *>(dst) + (size_t)(bs1 / g.decim) * eout;
+            return run_part(S, r, phase_now + bs1 * S->h_step[0], src2, src_q15, dst2, dst_q15, block_size - bs1, kAll, nullptr, block_size, nout);
+        }
+    }
+    return run_part(S, r, phase_now, src, src_q15, dst, dst_q15, block_size, phase, ext_env, block_size, nout);
+}
+
+// With an output stage the chain runs exactly as without one, into the instance's f32 audio buffer, and the stage kernel writes the caller's dst.
+// int16 slots: the fused kernels convert in and out symmetrically, so the input is converted up front (arm_q15_to_float over the whole
+// buffer, the operation the fused int16 load performs) and the call runs as an f32 call whose stage stores int16.
+int srx::run_chain(selenite_rx_instance *S, ChanRange r, CallStart at, const void *src, bool src_q15, void *dst, bool dst_q15,
+                   uint32_t block_size, Phase phase, float *ext_env)
+{
+    // an invariant, checked before anything is launched: both split entry points (rx_api.hip) refuse such an instance themselves, with
+    // their own message, so no C-ABI call gets here
+    if (S->out.on && phase != kAll) return fail(S, SELENITE_RX_ARGUMENT_ERROR, "the split global-gain calls exchange audio at the decimated rate: not with an output stage");
+    if (S->spec.len && phase != kPhase2)
+        if (int rc = S->spec.run(S, r, at.spec_pos, src, src_q15, block_size)) return rc;
+    if (!S->out.on) return run_chain_core(S, r, at.phase, src, src_q15, dst, dst_q15, block_size, phase, ext_env);
+    HIPCHK(S, hipSetDevice(S->device));
+    float *audio = nullptr;
+    if (int rc = S->out.audio_buffer(S, r, block_size, &audio)) return rc;
+    if (src_q15) {
+        const size_t nval = (size_t)r.count * block_size * 2;
+        if (int rc = ensure(S, (void **)&S->d_conv_in, &S->conv_in_bytes, nval * sizeof(float))) return rc;
+        HIPCHK(S, launch_q15_to_f32(static_cast<const int16_t *>(src), S->d_conv_in, nval, S->stream));
+        src = S->d_conv_in;
+    }
+    if (int rc = run_chain_core(S, r, at.phase, src, false, audio, false, block_size, kAll, nullptr)) return rc;
+    return S->out.run(S, r, audio, dst, dst_q15, block_size);
+}
+
+// global_phase2 advances nothing (its phase 1 did); the NCO phase moves only when the NCO runs
+void srx::advance_streams(selenite_rx_instance *S, uint32_t block_size, Phase phase)
+{
+    if (phase == kPhase2) return;
+    if (S->cfg.nco_enable) S->phase_host += block_size * S->h_step[0];
+    if (S->spec.len) S->spec.pos += block_size;
+}
+
+int srx::run_call(selenite_rx_instance *S, const void *src, bool src_q15, void *dst, bool dst_q15, uint32_t block_size, Phase phase, float *ext_env)
+{
+    if (int rc = run_chain(S, all_channels(S), call_start(S), src, src_q15, dst, dst_q15, block_size, phase, ext_env)) return rc;
+    advance_streams(S, block_size, phase);
+    return SELENITE_RX_SUCCESS;
+}
+
+// ---- global-gain call with the exchange done HERE, for a plain C host: phase 1, ncclAllReduce(MAX) of the
+// per-block envelopes over RCCL / xGMI, phase 2 -- all on the instance's stream.  RCCL is bound at run time
+// (the process's already loaded librccl -- e.g. the one torch ships -- or librccl.so.1), so the library carries no
+// link-time dependency on it and a host that never uses global gain never loads it.
+typedef int (*nccl_allreduce_fn)(const void *, void *, size_t, int, int, void *, hipStream_t);
+static nccl_allreduce_fn rccl_allreduce()
+{
+    static nccl_allreduce_fn fn = [] {
+        void *sym = dlsym(RTLD_DEFAULT, "ncclAllReduce");
+        if (!sym) {
+            void *h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
+            if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
+            if (h) sym = dlsym(h, "ncclAllReduce");
+        }
+        return reinterpret_cast<nccl_allreduce_fn>(sym);
+    }();
+    return fn;
+}
+
+extern "C" int selenite_rx_global_process_f32_device(selenite_rx_instance *S, const float *dSrcIQ, float *dDstAudio,
+                                                     uint32_t blockSize, void *rccl_comm)
+{
+    if (!S || !block_size_ok(S, blockSize, "selenite_rx_global_process_f32_device")) return S ? S->status : SELENITE_RX_ARGUMENT_ERROR;
+    if (!(S->cfg.agc_enable && S->cfg.agc_global))
+        return fail(S, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_global_process_f32_device: instance is not agc_global");
+    const size_t nblk = blockSize / S->cfg.block;
+    int rc = ensure(S, (void **)&S->d_env, &S->env_cap, sizeof(float) * nblk);
+    if (rc) return rc;
+    // (an output stage sits behind phase 2: both phases work on the instance's audio buffer, the stage writes dDstAudio)
+    const ChanRange r = all_channels(S);
+    const CallStart at = call_start(S);
+    float *audio = dDstAudio;
+    if (S->out.on && (rc = S->out.audio_buffer(S, r, blockSize, &audio))) return rc;
+    if (S->spec.len && (rc = S->spec.run(S, r, at.spec_pos, dSrcIQ, false, blockSize))) return rc;
+    rc = run_chain_core(S, r, at.phase, dSrcIQ, false, audio, false, blockSize, kPhase1, S->d_env);
+    if (rc) return rc;
+    if (rccl_comm) {                                        // NULL: single rank, nothing to exchange
+        nccl_allreduce_fn ar = rccl_allreduce();
+        if (!ar) return fail(S, SELENITE_RX_DEVICE_ERROR, "selenite_rx_global_process_f32_device: RCCL (ncclAllReduce) is not available");
+        const int nccl_float = 7, nccl_max = 2;             // ncclFloat32, ncclMax (rccl.h)
+        const int e = ar(S->d_env, S->d_env, nblk, nccl_float, nccl_max, rccl_comm, S->stream);
+        if (e != 0) return fail(S, SELENITE_RX_DEVICE_ERROR, "selenite_rx_global_process_f32_device: ncclAllReduce failed (" + std::to_string(e) + ")");
+    }
+    rc = run_chain_core(S, r, at.phase, nullptr, false, audio, false, blockSize, kPhase2, S->d_env);
+    if (!rc && S->out.on) rc = S->out.run(S, r, audio, dDstAudio, false, blockSize);
+    if (rc) return rc;
+    advance_streams(S, blockSize, kAll);
+    return SELENITE_RX_SUCCESS;
+}

@@ -591,12 +591,20 @@ hipError_t launch_hist_exact(const RxParams &p, bool all, hipStream_t st)
     return hipGetLastError();
 }
 
+// ... and the same conversion one value per thread and step: the calls k_q15_to_f32 cannot take (no whole number of eight-value groups, or
+// a source that is not 16-byte aligned -- int16 slots of the output stage)
+__global__ __launch_bounds__(256) void k_q15_to_f32_any(const int16_t *__restrict__ src, float *__restrict__ dst, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = q15_to_float(src[i]);
+}
+
 hipError_t launch_q15_to_f32(const int16_t *src, float *dst, size_t n, hipStream_t st)
 {
-    if (n % 8 != 0) return hipErrorInvalidValue;
-    const size_t n8 = n / 8;
-    const unsigned grid = (unsigned)((n8 + 255) / 256 < 16384 ? (n8 + 255) / 256 : 16384);
-    hipLaunchKernelGGL(k_q15_to_f32, dim3(grid ? grid : 1), dim3(256), 0, st, src, dst, n8);
+    const bool groups = n % 8 == 0 && reinterpret_cast<uintptr_t>(src) % 16 == 0;
+    const size_t work = groups ? n / 8 : n;
+    const unsigned grid = (unsigned)((work + 255) / 256 < 16384 ? (work + 255) / 256 : 16384);
+    if (groups) hipLaunchKernelGGL(k_q15_to_f32, dim3(grid ? grid : 1), dim3(256), 0, st, src, dst, work);
+    else hipLaunchKernelGGL(k_q15_to_f32_any, dim3(grid ? grid : 1), dim3(256), 0, st, src, dst, n);
     return hipGetLastError();
 }
 

@@ -10,7 +10,13 @@
 #include "rx_device.h"
 #include "rx_diag.h"
 
+struct selenite_rx_instance;
+
 namespace srx {
+
+// A contiguous range of the instance's channels: what one launch serves.  The whole instance is { 0, cfg.channels }; a chunk of a
+// host-pointer call (rx_hostpipe.hip) is a part of it.  count is never 0.  Every per-channel array moves with `first`.
+struct ChanRange { uint32_t first, count; };
 
 // Everything a kernel needs, passed by value (kernarg segment -> SGPRs).
 struct RxParams {
@@ -115,7 +121,7 @@ __host__ __device__ inline bool mode_is_upper(uint32_t m)
 hipError_t launch_front_generic(const RxParams &p, int arith, const void *src, bool src_q15,
                                 float *audio, hipStream_t st);
 size_t front_generic_lds_bytes(const RxParams &p);
-// arm_q15_to_float over a whole buffer (SupportFunctions/arm_q15_to_float.c:87): n int16 values -> n floats
+// arm_q15_to_float over a whole buffer (SupportFunctions/arm_q15_to_float.c:87): n int16 values -> n floats, any n and any alignment
 hipError_t launch_q15_to_f32(const int16_t *src, float *dst, size_t n, hipStream_t st);
 // SELENITE_ARITH_AUTO, in front of the rerun pass: the Hilbert-pair history of every flagged channel whose state the call before left
 // on the matrix kernel (with its hist_ext) is recomputed in exact arithmetic from hist_ext + the decimator state (rx_generic.hip)
@@ -137,7 +143,7 @@ hipError_t launch_agc_apply_global(const RxParams &p, int arith, const float *au
 
 // ---- NLMS noise reduction / automatic notch (rx_nlms.hip): in place on un-scaled f32 audio, between the demodulator and the AGC ----
 struct NrParams {
-    uint32_t channels;     // channels of this launch (a sub-range on the host-pointer path: the arrays below are offset to it)
+    uint32_t channels;     // channels of this launch (a ChanRange: the arrays below are offset to it)
     uint32_t nout;         // audio samples per channel in this call
     uint32_t stride;       // audio samples between consecutive channels (RxParams::out_stride)
     uint32_t delay;        // D
@@ -151,10 +157,20 @@ struct NrParams {
     uint32_t *flags;       // RxParams::flags (kFlagNanInf)
 };
 hipError_t launch_nlms(const NrParams &q, uint32_t num_taps, float *audio, hipStream_t st);
+// the stage's part of the instance (selenite_rx_set_nr): kind SELENITE_RX_NR_OFF = no stage, no buffers
+struct __attribute__((visibility("hidden"))) NrStage {
+    uint32_t kind = SELENITE_RX_NR_OFF, taps = 0, delay = 0;
+    float mu = 0.0f;
+    std::vector<float> h_init;         // [taps] the weights set_nr / reset start from
+    float *d_coeffs = nullptr, *d_window = nullptr, *d_delay = nullptr, *d_energy = nullptr, *d_x0 = nullptr;
+    void release();                                         // frees the buffers: no stage
+    int init_state(selenite_rx_instance *S);                // the state arm_lms_norm_init_f32 leaves
+    NrParams params(ChanRange r, const RxParams &p) const;  // the stage's view of a launch: the channels and the audio geometry of `p`
+};
 
 // ---- audio output stage (rx_out.hip): arm_fir_interpolate_f32 -> [arm_float_to_q15] -> mono / stereo frames, behind the AGC ----
 struct OutParams {
-    uint32_t channels;     // channels of this launch (a sub-range on the host-pointer path: `state` is offset to it)
+    uint32_t channels;     // channels of this launch (a ChanRange: `state` is offset to it)
     uint32_t nout;         // audio samples per channel in this call (input of the stage)
     uint32_t stride;       // audio samples between consecutive channels of `audio`
     uint32_t phase_len;    // P = ni_taps / interp; 0: no FIR (interp == 1), the samples pass as they are
@@ -167,12 +183,24 @@ struct OutParams {
 // bytes of one interpolated sample in dst
 inline uint32_t out_sample_bytes(bool stereo, bool q15) { return (q15 ? 2u : 4u) * (stereo ? 2u : 1u); }
 hipError_t launch_out(const OutParams &q, uint32_t interp, bool stereo, bool dst_q15, const float *audio, void *dst, hipStream_t st);
-// arm_q15_to_float over n values, any n (launch_q15_to_f32 wants whole groups of eight)
-hipError_t launch_q15_to_f32_any(const int16_t *src, float *dst, size_t n, hipStream_t st);
+// the stage's part of the instance (selenite_rx_set_out): on = false: no stage, no buffers
+struct __attribute__((visibility("hidden"))) OutStage {
+    bool on = false;
+    uint32_t interp = 1, taps = 0, frames = SELENITE_RX_OUT_MONO;
+    float *d_coeffs = nullptr, *d_state = nullptr;          // [taps] | [channels][taps / interp - 1]
+    float *d_audio = nullptr; size_t audio_bytes = 0;       // f32 audio of the chain in front of the stage, [channels of the launch][blockSize / decim]
+    void release();                                         // frees the buffers: no stage
+    int init_state(selenite_rx_instance *S);                // the state arm_fir_interpolate_init_f32 leaves
+    OutParams params(const selenite_rx_instance *S, ChanRange r, const void *dst, bool dst_q15, uint32_t block_size) const;
+    // d_audio, grown to the launch: where the chain writes in front of the stage
+    int audio_buffer(selenite_rx_instance *S, ChanRange r, uint32_t block_size, float **audio);
+    // the stage kernel, once over the whole call: `audio` (audio_buffer) -> the caller's dst
+    int run(selenite_rx_instance *S, ChanRange r, const float *audio, void *dst, bool dst_q15, uint32_t block_size) const;
+};
 
 // ---- spectrum tap (rx_spectrum.hip): window -> arm_cfft_f32 -> arm_cmplx_mag_squared_f32 -> averaged, display-ordered row, on the raw input ----
 struct SpecParams {
-    uint32_t channels;     // channels of this launch (a sub-range on the host-pointer path: rows and pending are offset to it)
+    uint32_t channels;     // channels of this launch (a ChanRange: rows and pending are offset to it)
     uint32_t block_size;   // input samples per channel in this call
     uint32_t in_stride;    // complex samples between consecutive channels of the source
     uint32_t off;          // samples of the call's first frame that arrived with earlier calls (stream position % fft_len)
@@ -180,12 +208,26 @@ struct SpecParams {
     uint32_t stride;
     uint32_t average;      // 1: row += alpha * (p - row); 0: row = p
     float alpha;
-    const float *tw;       // [fft_len][2] (cos, sin) (rx_api.hip: spec_twiddles)
+    const float *tw;       // [fft_len][2] (cos, sin) (rx_spectrum.hip: spec_twiddles)
     const float *window;   // [fft_len] or NULL
     float *rows;           // [C][fft_len] display order
     float *pending;        // [C][fft_len][2] the samples so far of the frame the stream stands in
 };
 hipError_t launch_spectrum(const SpecParams &q, uint32_t fft_len, const void *src, bool src_q15, hipStream_t st);
+// the stage's part of the instance (selenite_rx_set_spectrum): len = 0: no stage, no buffers
+struct __attribute__((visibility("hidden"))) SpecStage {
+    uint32_t len = 0, stride = 1, average = 0;
+    float alpha = 1.0f;
+    uint64_t pos = 0;                  // input samples per channel since set_spectrum / reset: advanced once per call (rx_dispatch.hip: advance_streams)
+    float *d_tw = nullptr, *d_window = nullptr;             // [len][2] | [len] or NULL
+    float *d_rows = nullptr, *d_pending = nullptr;          // [channels][len] | [channels][len][2]
+    void release();                                         // frees the buffers: no stage
+    int init_state(selenite_rx_instance *S);                // the state set_spectrum leaves
+    // false: a call of block_size samples that starts at stream position `at` touches no transformed frame -- nothing to launch
+    bool params(ChanRange r, uint64_t at, uint32_t block_size, SpecParams &q) const;
+    // one launch on the instance's stream, on the caller's own input (f32, or int16 read directly)
+    int run(selenite_rx_instance *S, ChanRange r, uint64_t at, const void *src, bool src_q15, uint32_t block_size) const;
+};
 // host: twiddleCoef_n regenerated, tw[n][2] = (cos, sin)(2 pi i / n) as the reference's table holds them
 void spec_twiddles(float *tw, uint32_t n);
 
@@ -284,7 +326,7 @@ struct selenite_rx_instance {
     float *d_env_part = nullptr; size_t env_part_cap = 0;   // per-wavefront envelope maxima
     void *d_io_in = nullptr;     size_t io_in_bytes = 0;     // staging for the host-pointer entry points (global-gain calls)
     void *d_io_out = nullptr;    size_t io_out_bytes = 0;
-    // chunked, double-buffered pipeline of the host-pointer entry points (rx_api.hip: process_host)
+    // chunked, double-buffered pipeline of the host-pointer entry points (rx_hostpipe.hip: process_host)
     struct HostPipe {
         hipStream_t h2d = nullptr, d2h = nullptr;
         hipEvent_t ev_in[2] = { nullptr, nullptr }, ev_done[2] = { nullptr, nullptr }, ev_out[2] = { nullptr, nullptr };
@@ -292,33 +334,19 @@ struct selenite_rx_instance {
         void *h_in[2] = { nullptr, nullptr }, *h_out[2] = { nullptr, nullptr };     // pinned staging (pageable callers only)
         size_t d_in_bytes = 0, d_out_bytes = 0, h_in_bytes = 0, h_out_bytes = 0;
     } pipe;
-    uint32_t sub_first = 0, sub_count = 0;                   // channel sub-range of the current launch (0 = all channels)
     float2 *d_lo = nullptr;      size_t lo_bytes = 0;        // shared LO table of the current call
     bool lo_valid = false; uint32_t lo_phase = 0, lo_step = 0, lo_n = 0;   // what d_lo holds: LO[n], n < lo_n, from (lo_phase, lo_step)
     bool steps_uniform = false;        // every channel has the same NCO step
     bool phase_uniform = true;         // ... and the same phase (true after init/reset)
-    uint32_t phase_host = 0;           // that common phase, tracked on the host
+    uint32_t phase_host = 0;           // that common phase, tracked on the host: advanced once per call (rx_dispatch.hip: advance_streams)
     bool delay_is_impulse = false; int delay_index = 0; bool hilb_odd_only = false;
     srx::FusedPlan plan;
     int no_shared_lo = 0;              // SELENITE_RX_NO_SHARED_LO=1: always compute the LO per channel
     int no_periodic_lo = 0;            // SELENITE_RX_NO_PERIODIC_LO=1: never keep a periodic shared LO in registers
     int force_generic = 0;             // SELENITE_RX_FORCE_GENERIC=1 (tests cross-check both paths)
-    // NLMS stage (selenite_rx_set_nr): kind SELENITE_RX_NR_OFF = no stage, no buffers
-    uint32_t nr_kind = SELENITE_RX_NR_OFF, nr_taps = 0, nr_delay = 0;
-    float nr_mu = 0.0f;
-    std::vector<float> h_nr_init;      // [nr_taps] the weights set_nr / reset start from
-    float *d_nr_coeffs = nullptr, *d_nr_window = nullptr, *d_nr_delay = nullptr, *d_nr_energy = nullptr, *d_nr_x0 = nullptr;
-    // audio output stage (selenite_rx_set_out): out_on = false: no stage, no buffers
-    bool out_on = false;
-    uint32_t out_interp = 1, out_taps = 0, out_frames = SELENITE_RX_OUT_MONO;
-    float *d_out_coeffs = nullptr, *d_out_state = nullptr;    // [out_taps] | [channels][out_taps / out_interp - 1]
-    float *d_out_audio = nullptr; size_t out_audio_bytes = 0;   // f32 audio of the chain in front of the stage, [channels][blockSize / decim]
-    // spectrum tap (selenite_rx_set_spectrum): spec_len = 0: no stage, no buffers
-    uint32_t spec_len = 0, spec_stride = 1, spec_average = 0;
-    float spec_alpha = 1.0f;
-    uint64_t spec_pos = 0;             // input samples per channel since set_spectrum / reset
-    float *d_spec_tw = nullptr, *d_spec_window = nullptr;      // [spec_len][2] | [spec_len] or NULL
-    float *d_spec_rows = nullptr, *d_spec_pending = nullptr;   // [channels][spec_len] | [channels][spec_len][2]
+    srx::NrStage nr;                   // NLMS noise reduction / automatic notch, in front of the AGC (rx_nlms.hip)
+    srx::OutStage out;                 // audio output stage, behind the chain (rx_out.hip)
+    srx::SpecStage spec;               // spectrum tap, in front of the chain (rx_spectrum.hip)
     int status = SELENITE_RX_SUCCESS;
     std::string err;
 };

@@ -15,7 +15,10 @@
 // recurrence, and eight samples of compute stand between a batch's loads and its ring writes.  Once u[n] is read its slot is dead and takes
 // the stage output of sample n; the outputs of tile t - 1 leave during tile t, batch by batch, the way the input came.  The eight samples
 // of a batch are unrolled, so the window's shift is a renaming of registers, not N - 1 moves per sample.
-#include "rx_internal.h"
+#include "rx_host.h"
+
+#include <cmath>
+#include <cstring>
 
 namespace srx {
 
@@ -202,4 +205,109 @@ hipError_t launch_nlms(const NrParams &q, uint32_t num_taps, float *audio, hipSt
     return hipGetLastError();
 }
 
+// ---- host side of the stage ----
+void NrStage::release()
+{
+    dev_free(d_coeffs, d_window, d_delay, d_energy, d_x0);
+    kind = SELENITE_RX_NR_OFF;
+    taps = delay = 0;
+    mu = 0.0f;
+    h_init.clear();
+}
+
+// the NLMS stage's state as arm_lms_norm_init_f32 leaves it (arm_lms_norm_init_f32.c:69-86): weights = the initial ones, the rest 0
+int NrStage::init_state(selenite_rx_instance *S)
+{
+    if (kind == SELENITE_RX_NR_OFF) return SELENITE_RX_SUCCESS;
+    const size_t C = S->cfg.channels, N = taps, D = delay;
+    std::vector<float> w(C * N);
+    for (size_t c = 0; c < C; ++c) std::memcpy(&w[c * N], h_init.data(), N * sizeof(float));
+    HIPCHK(S, hipMemcpyAsync(d_coeffs, w.data(), C * N * sizeof(float), hipMemcpyHostToDevice, S->stream));
+    HIPCHK(S, hipMemsetAsync(d_window, 0, C * (N - 1) * sizeof(float), S->stream));
+    HIPCHK(S, hipMemsetAsync(d_delay, 0, C * D * sizeof(float), S->stream));
+    HIPCHK(S, hipMemsetAsync(d_energy, 0, C * sizeof(float), S->stream));
+    HIPCHK(S, hipMemsetAsync(d_x0, 0, C * sizeof(float), S->stream));
+    HIPCHK(S, hipStreamSynchronize(S->stream));      // (w is a host temporary)
+    return SELENITE_RX_SUCCESS;
+}
+
+NrParams NrStage::params(ChanRange r, const RxParams &p) const
+{
+    const size_t c0 = r.first;
+    NrParams q{};
+    q.channels = p.channels; q.nout = p.nout; q.stride = p.out_stride;
+    q.delay = delay; q.notch = kind == SELENITE_RX_NR_NOTCH ? 1u : 0u; q.mu = mu;
+    q.coeffs = d_coeffs + c0 * taps; q.window = d_window + c0 * (taps - 1); q.delay_line = d_delay + c0 * delay;
+    q.energy = d_energy + c0; q.x0 = d_x0 + c0;
+    q.flags = p.flags;
+    return q;
+}
+
 }  // namespace srx
+
+using namespace srx;
+
+extern "C" int selenite_rx_set_nr(selenite_rx_instance *S, const selenite_rx_nr_config *nr)
+{
+    if (!S) return fail(nullptr, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_set_nr: S is NULL");
+    // everything is validated before anything changes: a refused call leaves the instance as it was
+    if (nr && nr->struct_size != sizeof(selenite_rx_nr_config)) {
+        last_error() = "selenite_rx_set_nr: struct_size is not sizeof(selenite_rx_nr_config)";
+        return SELENITE_RX_ARGUMENT_ERROR;
+    }
+    if (nr && nr->kind != SELENITE_RX_NR_OFF) {
+        const uint32_t N = nr->num_taps;
+        const char *bad = nullptr;
+        if (nr->kind != SELENITE_RX_NR_DENOISE && nr->kind != SELENITE_RX_NR_NOTCH) bad = "kind is not a SELENITE_RX_NR_* value";
+        else if (N != 8 && N != 16 && N != 32 && N != 64) bad = "num_taps is not 8, 16, 32 or 64";
+        else if (nr->delay < 1 || nr->delay > 64) bad = "delay is not 1 .. 64";
+        else if (!(nr->mu > 0.0f && nr->mu < 2.0f)) bad = "mu is not finite in (0, 2)";
+        else if (nr->coeffs_init)
+            for (uint32_t k = 0; k < N && !bad; ++k)
+                if (!std::isfinite(nr->coeffs_init[k])) bad = "coeffs_init holds a non-finite weight";
+        if (bad) {
+            last_error() = std::string("selenite_rx_set_nr: ") + bad;
+            return SELENITE_RX_ARGUMENT_ERROR;
+        }
+    }
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    NrStage &st = S->nr;
+    st.release();
+    if (!nr || nr->kind == SELENITE_RX_NR_OFF) return SELENITE_RX_SUCCESS;
+    const size_t C = S->cfg.channels, N = nr->num_taps, D = nr->delay;
+    st.h_init.assign(N, 0.0f);
+    if (nr->coeffs_init) std::memcpy(st.h_init.data(), nr->coeffs_init, N * sizeof(float));
+    hipError_t e = dev_alloc(&st.d_coeffs, C * N);
+    if (e == hipSuccess) e = dev_alloc(&st.d_window, C * (N - 1));
+    if (e == hipSuccess) e = dev_alloc(&st.d_delay, C * D);
+    if (e == hipSuccess) e = dev_alloc(&st.d_energy, C);
+    if (e == hipSuccess) e = dev_alloc(&st.d_x0, C);
+    if (e != hipSuccess) {
+        st.release();
+        return fail(S, SELENITE_RX_DEVICE_ERROR, std::string("selenite_rx_set_nr: hipMalloc: ") + hipGetErrorString(e));
+    }
+    st.kind = nr->kind; st.taps = (uint32_t)N; st.delay = (uint32_t)D; st.mu = nr->mu;
+    return st.init_state(S);
+}
+
+// the five arrays of selenite_rx_nr_state_view copied out of the device (to_host) or into it
+static int nr_state_copy(selenite_rx_instance *S, const selenite_rx_nr_state_view *v, bool to_host)
+{
+    if (!S || !v || S->nr.kind == SELENITE_RX_NR_OFF) return SELENITE_RX_ARGUMENT_ERROR;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    const NrStage &st = S->nr;
+    const size_t C = S->cfg.channels;
+    float *dev[5] = { st.d_coeffs, st.d_window, st.d_delay, st.d_energy, st.d_x0 };
+    float *host[5] = { v->coeffs, v->window, v->delay, v->energy, v->x0 };
+    const size_t n[5] = { C * st.taps, C * (st.taps - 1), C * st.delay, C, C };
+    for (int i = 0; i < 5; ++i) {
+        if (!host[i] || !n[i]) continue;
+        if (to_host) HIPCHK(S, hipMemcpy(host[i], dev[i], n[i] * sizeof(float), hipMemcpyDeviceToHost));
+        else HIPCHK(S, hipMemcpy(dev[i], host[i], n[i] * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return SELENITE_RX_SUCCESS;
+}
+extern "C" int selenite_rx_get_nr_state(selenite_rx_instance *S, const selenite_rx_nr_state_view *v) { return nr_state_copy(S, v, true); }
+extern "C" int selenite_rx_set_nr_state(selenite_rx_instance *S, const selenite_rx_nr_state_view *v) { return nr_state_copy(S, v, false); }

@@ -15,7 +15,9 @@
 // A lane owns 16 consecutive bytes of the output row: 4 f32 / 2 f32 pairs / 8 int16 / 4 int16 pairs, packed to four dwords and stored as one
 // non-temporal global_store_dwordx4 -- a wave store covers 1 KiB of the row; the audio, written a moment ago by the chain, is read with
 // default (cached) loads.  Rows that are not 16-byte multiples (or a dst that is not 16-byte aligned) take element stores (OutParams::vec).
-#include "rx_internal.h"
+#include "rx_host.h"
+
+#include <cmath>
 
 namespace srx {
 
@@ -164,19 +166,115 @@ hipError_t launch_out(const OutParams &q, uint32_t interp, bool stereo, bool dst
     return hipGetLastError();
 }
 
-// arm_q15_to_float (SupportFunctions/arm_q15_to_float.c:87) over n values, any n and any alignment: the int16 slots of the output stage whose
-// call is no whole number of eight-value groups (launch_q15_to_f32 serves every other call)
-__global__ __launch_bounds__(256) void k_q15_to_f32_any(const int16_t *__restrict__ src, float *__restrict__ dst, size_t n)
+// ---- host side of the stage ----
+void OutStage::release()
 {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = q15_to_float(src[i]);
+    dev_free(d_coeffs, d_state, d_audio);
+    audio_bytes = 0;
+    on = false;
+    interp = 1; taps = 0; frames = SELENITE_RX_OUT_MONO;
 }
 
-hipError_t launch_q15_to_f32_any(const int16_t *src, float *dst, size_t n, hipStream_t st)
+// the output stage's state as arm_fir_interpolate_init_f32 leaves it (arm_fir_interpolate_init_f32.c:101-104): cleared
+int OutStage::init_state(selenite_rx_instance *S)
 {
-    if (n % 8 == 0 && reinterpret_cast<uintptr_t>(src) % 16 == 0) return launch_q15_to_f32(src, dst, n, st);
-    const unsigned grid = (unsigned)((n + 255) / 256 < 16384 ? (n + 255) / 256 : 16384);
-    hipLaunchKernelGGL(k_q15_to_f32_any, dim3(grid ? grid : 1), dim3(256), 0, st, src, dst, n);
-    return hipGetLastError();
+    if (!on || taps / interp < 2) return SELENITE_RX_SUCCESS;
+    const size_t n = (size_t)S->cfg.channels * (taps / interp - 1);
+    HIPCHK(S, hipMemsetAsync(d_state, 0, n * sizeof(float), S->stream));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    return SELENITE_RX_SUCCESS;
+}
+
+OutParams OutStage::params(const selenite_rx_instance *S, ChanRange r, const void *dst, bool dst_q15, uint32_t block_size) const
+{
+    OutParams q{};
+    q.channels = r.count;
+    q.nout = block_size / S->cfg.decim; q.stride = q.nout;
+    q.phase_len = taps / interp;
+    q.q15_round = S->cfg.q15_rounding ? 1u : 0u;
+    const size_t row_bytes = (size_t)q.nout * interp * out_sample_bytes(frames == SELENITE_RX_OUT_STEREO, dst_q15);
+    q.vec = (reinterpret_cast<uintptr_t>(dst) % 16 == 0 && row_bytes % 16 == 0) ? 1u : 0u;
+    q.coeffs = d_coeffs;
+    q.state = d_state ? d_state + (size_t)r.first * (q.phase_len - 1) : nullptr;
+    q.flags = S->d_flags;
+    return q;
+}
+
+// grown, never allocated per call
+int OutStage::audio_buffer(selenite_rx_instance *S, ChanRange r, uint32_t block_size, float **audio)
+{
+    int rc = ensure(S, (void **)&d_audio, &audio_bytes, (size_t)r.count * (block_size / S->cfg.decim) * sizeof(float));
+    *audio = d_audio;
+    return rc;
+}
+
+int OutStage::run(selenite_rx_instance *S, ChanRange r, const float *audio, void *dst, bool dst_q15, uint32_t block_size) const
+{
+    HIPCHK(S, launch_out(params(S, r, dst, dst_q15, block_size), interp, frames == SELENITE_RX_OUT_STEREO, dst_q15, audio, dst, S->stream));
+    return SELENITE_RX_SUCCESS;
 }
 
 }  // namespace srx
+
+using namespace srx;
+
+extern "C" int selenite_rx_set_out(selenite_rx_instance *S, const selenite_rx_out_config *out)
+{
+    if (!S) return fail(nullptr, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_set_out: S is NULL");
+    // everything is validated before anything changes: a refused call leaves the instance as it was
+    if (out) {
+        const uint32_t L = out->interp;
+        const char *bad = nullptr;
+        int code = SELENITE_RX_ARGUMENT_ERROR;
+        if (out->struct_size != sizeof(selenite_rx_out_config)) bad = "struct_size is not sizeof(selenite_rx_out_config)";
+        else if (L != 1 && L != 2 && L != 4 && L != 8) bad = "interp is not 1, 2, 4 or 8";
+        else if (out->ni_taps % L != 0) { bad = "ni_taps is not a multiple of interp"; code = SELENITE_RX_LENGTH_ERROR; }   // arm_fir_interpolate_init_f32.c:91-96
+        else if (out->ni_taps / L > 64 || (out->ni_taps == 0 && L != 1)) bad = "ni_taps / interp is not 1 .. 64 (0 taps: interp 1 only)";
+        else if (out->frames != SELENITE_RX_OUT_MONO && out->frames != SELENITE_RX_OUT_STEREO) bad = "frames is not a SELENITE_RX_OUT_* value";
+        else if (out->ni_taps && !out->coeffs) bad = "coeffs is NULL";
+        else
+            for (uint32_t k = 0; k < out->ni_taps && !bad; ++k)
+                if (!std::isfinite(out->coeffs[k])) bad = "coeffs holds a non-finite tap";
+        if (bad) {
+            last_error() = std::string("selenite_rx_set_out: ") + bad;
+            return code;
+        }
+    }
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    OutStage &st = S->out;
+    st.release();
+    if (!out) return SELENITE_RX_SUCCESS;
+    const size_t C = S->cfg.channels, P = out->ni_taps / out->interp;
+    hipError_t e = dev_upload(&st.d_coeffs, out->coeffs, (size_t)out->ni_taps);
+    if (e == hipSuccess) e = dev_alloc(&st.d_state, P > 1 ? C * (P - 1) : 0);
+    if (e != hipSuccess) {
+        st.release();
+        return fail(S, SELENITE_RX_DEVICE_ERROR, std::string("selenite_rx_set_out: hipMalloc: ") + hipGetErrorString(e));
+    }
+    st.on = true; st.interp = out->interp; st.taps = out->ni_taps; st.frames = out->frames;
+    return st.init_state(S);
+}
+
+extern "C" uint32_t selenite_rx_out_values(const selenite_rx_instance *S, uint32_t blockSize)
+{
+    if (!S) return 0;
+    const uint32_t n = blockSize / S->cfg.decim;
+    return S->out.on ? n * S->out.interp * (S->out.frames == SELENITE_RX_OUT_STEREO ? 2u : 1u) : n;
+}
+
+static int out_state_copy(selenite_rx_instance *S, float *host, bool to_host)
+{
+    if (!S || !host || !S->out.on || S->out.taps / S->out.interp < 2) return SELENITE_RX_ARGUMENT_ERROR;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    const size_t bytes = (size_t)S->cfg.channels * (S->out.taps / S->out.interp - 1) * sizeof(float);
+    if (to_host) HIPCHK(S, hipMemcpy(host, S->out.d_state, bytes, hipMemcpyDeviceToHost));
+    else HIPCHK(S, hipMemcpy(S->out.d_state, host, bytes, hipMemcpyHostToDevice));
+    return SELENITE_RX_SUCCESS;
+}
+extern "C" int selenite_rx_get_out_state(selenite_rx_instance *S, float *interp_state) { return out_state_copy(S, interp_state, true); }
+extern "C" int selenite_rx_set_out_state(selenite_rx_instance *S, const float *interp_state)
+{
+    return out_state_copy(S, const_cast<float *>(interp_state), false);
+}

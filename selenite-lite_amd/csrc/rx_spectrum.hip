@@ -23,7 +23,7 @@
 // TRANSFORMED frames, so a stride leaves no lane idle); their powers go through LDS to lane k = display index, which averages them in order.
 // The row lives in registers across the frames of a call: read once (averaging only) and written once per call.  The pending frame is read
 // only by a call that starts inside a transformed frame and written only by one that ends inside one; skipped frames are never read.
-#include "rx_internal.h"
+#include "rx_host.h"
 
 #include <cmath>
 #include <cstdio>
@@ -245,7 +245,129 @@ hipError_t launch_spectrum(const SpecParams &q, uint32_t fft_len, const void *sr
     return hipGetLastError();
 }
 
+// ---- host side of the stage ----
+void SpecStage::release()
+{
+    dev_free(d_tw, d_window, d_rows, d_pending);
+    len = 0; stride = 1; average = 0; alpha = 1.0f; pos = 0;
+}
+
+// the spectrum tap's state as set_spectrum leaves it: rows +0.0f, no pending samples, position 0
+int SpecStage::init_state(selenite_rx_instance *S)
+{
+    if (!len) return SELENITE_RX_SUCCESS;
+    const size_t n = (size_t)S->cfg.channels * len;
+    HIPCHK(S, hipMemsetAsync(d_rows, 0, n * sizeof(float), S->stream));
+    HIPCHK(S, hipMemsetAsync(d_pending, 0, 2 * n * sizeof(float), S->stream));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    pos = 0;
+    return SELENITE_RX_SUCCESS;
+}
+
+bool SpecStage::params(ChanRange r, uint64_t at, uint32_t block_size, SpecParams &q) const
+{
+    const uint32_t N = len;
+    const uint64_t f0 = at / N;
+    q = SpecParams{};
+    q.off = (uint32_t)(at % N);
+    q.first = (uint32_t)((stride - f0 % stride) % stride);
+    if (((uint64_t)q.off + block_size - 1) / N < q.first) return false;      // the frames the call touches are all skipped ones
+    q.channels = r.count;
+    q.block_size = block_size; q.in_stride = block_size;
+    q.stride = stride; q.average = average; q.alpha = alpha;
+    q.tw = d_tw; q.window = d_window;
+    q.rows = d_rows + (size_t)r.first * N; q.pending = d_pending + (size_t)r.first * N * 2;
+    return true;
+}
+
+// Step 0b: in front of everything else.  A call that touches no transformed frame launches nothing.
+int SpecStage::run(selenite_rx_instance *S, ChanRange r, uint64_t at, const void *src, bool src_q15, uint32_t block_size) const
+{
+    SpecParams q;
+    if (!params(r, at, block_size, q)) return SELENITE_RX_SUCCESS;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, launch_spectrum(q, len, src, src_q15, S->stream));
+    return SELENITE_RX_SUCCESS;
+}
+
 }  // namespace srx
+
+using namespace srx;
+
+extern "C" int selenite_rx_set_spectrum(selenite_rx_instance *S, const selenite_rx_spec_config *sp)
+{
+    if (!S) return fail(nullptr, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_set_spectrum: S is NULL");
+    // everything is validated before anything changes: a refused call leaves the instance as it was
+    if (sp) {
+        const char *bad = nullptr;
+        int code = SELENITE_RX_ARGUMENT_ERROR;
+        if (sp->struct_size != sizeof(selenite_rx_spec_config)) bad = "struct_size is not sizeof(selenite_rx_spec_config)";
+        else if (sp->fft_len != 64 && sp->fft_len != 512) { bad = "fft_len is not 64 or 512 (the pure radix-8 lengths of arm_cfft_f32)"; code = SELENITE_RX_LENGTH_ERROR; }
+        else if (sp->stride < 1 || sp->stride > 65535) bad = "stride is not 1 .. 65535";
+        else if (sp->average > 1) bad = "average is not 0 or 1";
+        else if (!(sp->alpha > 0.0f && sp->alpha <= 1.0f)) bad = "alpha is not finite in (0, 1]";
+        else if (sp->window)
+            for (uint32_t k = 0; k < sp->fft_len && !bad; ++k)
+                if (!std::isfinite(sp->window[k])) bad = "window holds a non-finite value";
+        if (bad) {
+            last_error() = std::string("selenite_rx_set_spectrum: ") + bad;
+            return code;
+        }
+    }
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    SpecStage &st = S->spec;
+    st.release();
+    if (!sp) return SELENITE_RX_SUCCESS;
+    const size_t C = S->cfg.channels, N = sp->fft_len;
+    std::vector<float> tw(2 * N);
+    spec_twiddles(tw.data(), (uint32_t)N);
+    hipError_t e = dev_upload(&st.d_tw, tw.data(), 2 * N);
+    if (e == hipSuccess && sp->window) e = dev_upload(&st.d_window, sp->window, N);
+    if (e == hipSuccess) e = dev_alloc(&st.d_rows, C * N);
+    if (e == hipSuccess) e = dev_alloc(&st.d_pending, C * N * 2);
+    if (e != hipSuccess) {
+        st.release();
+        return fail(S, SELENITE_RX_DEVICE_ERROR, std::string("selenite_rx_set_spectrum: hipMalloc: ") + hipGetErrorString(e));
+    }
+    st.len = (uint32_t)N; st.stride = sp->stride; st.average = sp->average; st.alpha = sp->alpha;
+    return st.init_state(S);
+}
+
+extern "C" int selenite_rx_get_spectrum(selenite_rx_instance *S, float *rows, uint64_t *frames)
+{
+    if (!S || !S->spec.len) return SELENITE_RX_ARGUMENT_ERROR;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    const SpecStage &st = S->spec;
+    if (rows) HIPCHK(S, hipMemcpy(rows, st.d_rows, (size_t)S->cfg.channels * st.len * sizeof(float), hipMemcpyDeviceToHost));
+    // frames transformed since set_spectrum / reset: the complete frames f < pos / N with f % stride == 0
+    if (frames) *frames = (st.pos / st.len + st.stride - 1) / st.stride;
+    return SELENITE_RX_SUCCESS;
+}
+
+extern "C" const float *selenite_rx_spectrum_device(const selenite_rx_instance *S) { return S ? S->spec.d_rows : nullptr; }
+
+static int spec_state_copy(selenite_rx_instance *S, const selenite_rx_spec_state_view *v, bool to_host)
+{
+    if (!S || !v || !S->spec.len) return SELENITE_RX_ARGUMENT_ERROR;
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    SpecStage &st = S->spec;
+    const size_t n = (size_t)S->cfg.channels * st.len * sizeof(float);
+    if (to_host) {
+        if (v->rows) HIPCHK(S, hipMemcpy(v->rows, st.d_rows, n, hipMemcpyDeviceToHost));
+        if (v->pending) HIPCHK(S, hipMemcpy(v->pending, st.d_pending, 2 * n, hipMemcpyDeviceToHost));
+        if (v->position) *v->position = st.pos;
+    } else {
+        if (v->rows) HIPCHK(S, hipMemcpy(st.d_rows, v->rows, n, hipMemcpyHostToDevice));
+        if (v->pending) HIPCHK(S, hipMemcpy(st.d_pending, v->pending, 2 * n, hipMemcpyHostToDevice));
+        if (v->position) st.pos = *v->position;
+    }
+    return SELENITE_RX_SUCCESS;
+}
+extern "C" int selenite_rx_get_spectrum_state(selenite_rx_instance *S, const selenite_rx_spec_state_view *v) { return spec_state_copy(S, v, true); }
+extern "C" int selenite_rx_set_spectrum_state(selenite_rx_instance *S, const selenite_rx_spec_state_view *v) { return spec_state_copy(S, v, false); }
 
 extern "C" int selenite_rx_spectrum_twiddles(float *tw, uint32_t fft_len)
 {

@@ -406,7 +406,7 @@ extern "C" int selenite_tx_init(selenite_tx_instance **out, const selenite_tx_co
     S->steps_same = true;
     for (size_t c = 1; c < C; ++c) S->steps_same = S->steps_same && S->h_step[c] == S->h_step[0];
     {   // what tx_fused.hip relies on: a unit-impulse delay FIR and a type-III Hilbert (taps at even
-        // distance from the centre exactly +0.0f) -- same classification as the RX side (rx_api.hip)
+        // distance from the centre exactly +0.0f) -- same classification as the RX side (rx_api.hip: classify_coeffs)
         const uint32_t nh = g->nh_taps;
         int ones = 0, idx = -1;
         bool rest_zero = true;

@@ -1,5 +1,5 @@
 """PCIe-inclusive rate of the host-buffer entry points selenite_rx_process_f32 / _q15 -- the literal drop-in
-call of the slot: chunked H2D || kernels || D2H pipeline inside the library (rx_api.hip: process_host).  Measured
+call of the slot: chunked H2D || kernels || D2H pipeline inside the library (rx_hostpipe.hip: process_host).  Measured
 with pageable caller memory (staged through the library's pinned buffers) and with page-locked caller memory
 (selenite_rx_host_alloc), next to the raw PCIe rate of one big pinned hipMemcpy.  DESIGN.md section 6 quotes this."""
 import os
