@@ -252,6 +252,42 @@ typedef struct selenite_rx_spec_state_view {
     uint64_t *position;
 } selenite_rx_spec_state_view;
 
+/* ---- impulse noise blanker (step 0c of DESIGN.md section 2, on the raw input I/Q behind the spectrum tap and in front of the NCO; off by
+ * default) ---------------------------------------------------------------------------------------------------------------------------
+ * The third of the classic NR / ANF / NB set, and the one that belongs at the input rate: one sample far above the band level rings through
+ * the decimator and the Hilbert pair and pumps the AGC; behind the demodulator nothing undoes that.  Every mode, every arith mode.  The
+ * call's input (int16 slots seen through arm_q15_to_float) is cut into frames of `frame` consecutive complex samples; frame divides
+ * cfg.block and every call is a whole number of DSP blocks, so nothing is left pending.  Per channel one float of state, level (+0.0f after
+ * set_nb and reset), and two counters.  Per frame, every operation rounded to f32, no contraction, denormals kept:
+ *   p[n] = arm_cmplx_mag_squared_f32(frame)           ComplexMathFunctions/arm_cmplx_mag_squared_f32.c: re * re + im * im
+ *   m    = arm_mean_f32(p, frame)                     StatisticsFunctions/arm_mean_f32.c:67-120: s = 0; s = s + p[n], n ascending; s / frame
+ *   !(level > 0) (not primed: zero, negative, NaN):   nothing is blanked; level = m
+ *   level > 0:  hit[n] = p[n] > threshold * level; k = the number of hits
+ *               1 <= k <= max_hits: sample n is blanked iff a hit lies within `guard` samples of it, inside the frame
+ *               k > max_hits: a signal that came up, not impulse noise: nothing is blanked, bursts += 1
+ *               level = level + alpha * (min(m, clamp * level) - level)     (the AGC's form; m < c ? m : c)
+ * The level does not depend on what was blanked: an impulse raises it by at most `clamp` per frame.  A blanked sample becomes (+0.0f, +0.0f)
+ * or (0, 0) and counts in `blanked`; every other sample is passed on as the bits it is (-0.0f, NaN payloads, -32768).  The chain then runs
+ * on that copy in place of the caller's input, in the caller's format; the spectrum tap keeps reading the caller's own.  Bit-exact against
+ * that composition.  The stage never raises SELENITE_RX_NANINF: that status keeps meaning audio (a NaN power is not a hit). */
+typedef struct selenite_rx_nb_config {
+    uint32_t struct_size;     /* = sizeof(selenite_rx_nb_config) (this struct's own growth path) */
+    uint32_t frame;           /* F: 32, 64 or 128, and a divisor of cfg.block; anything else is a SELENITE_RX_LENGTH_ERROR */
+    uint32_t guard;           /* 0 .. 8 samples on either side of a hit */
+    uint32_t max_hits;        /* 1 .. F / 4 */
+    float threshold;          /* finite, >= 1: sample power over level */
+    float alpha;              /* 0 < alpha <= 1 */
+    float clamp;              /* finite, >= 1 */
+} selenite_rx_nb_config;
+
+/* The blanker's whole state, each [channels]: level; blanked: samples blanked since set_nb / reset; bursts: frames with more than max_hits
+ * hits since then.  NULL members are skipped. */
+typedef struct selenite_rx_nb_state_view {
+    float *level;
+    uint64_t *blanked;
+    uint64_t *bursts;
+} selenite_rx_nb_state_view;
+
 typedef struct selenite_rx_instance selenite_rx_instance;  /* opaque; state lives in HBM */
 
 /* ---- instance life cycle ------------------------------------------------------------- */
@@ -427,6 +463,19 @@ int selenite_rx_set_spectrum_state(selenite_rx_instance *S, const selenite_rx_sp
 /* Host only, no device: the table the kernel uses, tw[fft_len][2] = (cos, sin)(2 pi i / fft_len) -- twiddleCoef_64 / twiddleCoef_512
  * (CommonTables/arm_common_tables.c) entry for entry: each is the float of the nine-decimal rendering of the double value. */
 int selenite_rx_spectrum_twiddles(float *tw, uint32_t fft_len);
+
+/* ---- impulse noise blanker --------------------------------------------------------------- */
+
+/* Sets the blanker for every channel (selenite_rx_nb_config), or removes it (nb == NULL).  Clears the blanker's state and nothing else.  A
+ * bad field (frame: SELENITE_RX_LENGTH_ERROR, any other: SELENITE_RX_ARGUMENT_ERROR) leaves the instance as it was, a working blanker
+ * included.  selenite_rx_set_mode, _set_nr, _set_out and _set_spectrum leave it alone; selenite_rx_reset returns level and both counters to
+ * zero.  Every process entry point that has input runs it once per call (f32 and int16 slots, device and host pointers, the timing calls,
+ * global phase 1, selenite_rx_global_process_f32_device -- not phase 2, not the roof timing calls).  The blanked copy lives in a buffer of
+ * the instance, grown by the first call that needs it.  With the blanker off no launch, byte, allocation or output of any call changes. */
+int selenite_rx_set_nb(selenite_rx_instance *S, const selenite_rx_nb_config *nb);
+/* Host copies of the state.  Drains the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the blanker is off. */
+int selenite_rx_get_nb_state(selenite_rx_instance *S, const selenite_rx_nb_state_view *dst);
+int selenite_rx_set_nb_state(selenite_rx_instance *S, const selenite_rx_nb_state_view *src);
 
 void *selenite_rx_device_alloc(size_t bytes);          /* hipMalloc; NULL on failure */
 void  selenite_rx_device_free(void *dptr);

@@ -1,6 +1,6 @@
 // rx_dispatch.hip -- the one dispatcher behind every process entry point: which kernels serve a call, over which channels
-// (ChanRange), from which stream positions (CallStart).  The three stages hook in here and nowhere else: the spectrum tap in front
-// of the chain, NLMS in front of the AGC, the output stage behind the chain.
+// (ChanRange), from which stream positions (CallStart).  The four stages hook in here and nowhere else: the spectrum tap and the noise
+// blanker in front of the chain, NLMS in front of the AGC, the output stage behind the chain.
 #include "rx_host.h"
 
 #include <dlfcn.h>
@@ -289,6 +289,9 @@ int srx::run_chain(selenite_rx_instance *S, ChanRange r, CallStart at, const voi
     if (S->out.on && phase != kAll) return fail(S, SELENITE_RX_ARGUMENT_ERROR, "the split global-gain calls exchange audio at the decimated rate: not with an output stage");
     if (S->spec.len && phase != kPhase2)
         if (int rc = S->spec.run(S, r, at.spec_pos, src, src_q15, block_size)) return rc;
+    // step 0c: from here on the chain reads the blanked copy of the input (the tap above has read the caller's own)
+    if (S->nb.frame && phase != kPhase2)
+        if (int rc = S->nb.run(S, r, src, src_q15, block_size, &src)) return rc;
     if (!S->out.on) return run_chain_core(S, r, at.phase, src, src_q15, dst, dst_q15, block_size, phase, ext_env);
     HIPCHK(S, hipSetDevice(S->device));
     float *audio = nullptr;
@@ -352,7 +355,9 @@ extern "C" int selenite_rx_global_process_f32_device(selenite_rx_instance *S, co
     float *audio = dDstAudio;
     if (S->out.on && (rc = S->out.audio_buffer(S, r, blockSize, &audio))) return rc;
     if (S->spec.len && (rc = S->spec.run(S, r, at.spec_pos, dSrcIQ, false, blockSize))) return rc;
-    rc = run_chain_core(S, r, at.phase, dSrcIQ, false, audio, false, blockSize, kPhase1, S->d_env);
+    const void *in = dSrcIQ;
+    if (S->nb.frame && (rc = S->nb.run(S, r, dSrcIQ, false, blockSize, &in))) return rc;
+    rc = run_chain_core(S, r, at.phase, in, false, audio, false, blockSize, kPhase1, S->d_env);
     if (rc) return rc;
     if (rccl_comm) {                                        // NULL: single rank, nothing to exchange
         nccl_allreduce_fn ar = rccl_allreduce();

@@ -231,6 +231,31 @@ struct __attribute__((visibility("hidden"))) SpecStage {
 // host: twiddleCoef_n regenerated, tw[n][2] = (cos, sin)(2 pi i / n) as the reference's table holds them
 void spec_twiddles(float *tw, uint32_t n);
 
+// ---- impulse noise blanker (rx_nb.hip): frame power -> arm_mean_f32 -> level, hits over threshold * level blanked, on the raw input ----
+struct NbParams {
+    uint32_t channels;     // channels of this launch (a ChanRange: level and the counters are offset to it)
+    uint32_t block_size;   // input samples per channel in this call = complex samples between consecutive channels of source and copy
+    uint32_t guard;        // samples blanked on either side of a hit
+    uint32_t max_hits;     // more hits than this in a frame: a burst, nothing blanked
+    float threshold, alpha, clamp;
+    float *level;          // [C]
+    uint64_t *blanked;     // [C] samples blanked so far
+    uint64_t *bursts;      // [C] frames with more than max_hits hits so far
+};
+hipError_t launch_nb(const NbParams &q, uint32_t frame, const void *src, bool src_q15, void *dst, hipStream_t st);
+// the stage's part of the instance (selenite_rx_set_nb): frame = 0: no stage, no buffers
+struct __attribute__((visibility("hidden"))) NbStage {
+    uint32_t frame = 0, guard = 0, max_hits = 0;
+    float threshold = 0.0f, alpha = 0.0f, clamp = 0.0f;
+    float *d_level = nullptr;                               // [channels]
+    uint64_t *d_blanked = nullptr, *d_bursts = nullptr;     // [channels] each
+    void *d_buf = nullptr; size_t buf_bytes = 0;            // the blanked copy of a call's input, [channels of the launch][blockSize][2], f32 or int16
+    void release();                                         // frees the buffers: no stage
+    int init_state(selenite_rx_instance *S);                // the state set_nb leaves
+    // one launch on the instance's stream: `src` (f32, or int16 as it is) -> d_buf, grown to the launch; *blanked_src = d_buf
+    int run(selenite_rx_instance *S, ChanRange r, const void *src, bool src_q15, uint32_t block_size, const void **blanked_src);
+};
+
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
     int kind = 0;                 // 0 = none
@@ -347,6 +372,7 @@ struct selenite_rx_instance {
     srx::NrStage nr;                   // NLMS noise reduction / automatic notch, in front of the AGC (rx_nlms.hip)
     srx::OutStage out;                 // audio output stage, behind the chain (rx_out.hip)
     srx::SpecStage spec;               // spectrum tap, in front of the chain (rx_spectrum.hip)
+    srx::NbStage nb;                   // impulse noise blanker, between the spectrum tap and the chain (rx_nb.hip)
     int status = SELENITE_RX_SUCCESS;
     std::string err;
 };

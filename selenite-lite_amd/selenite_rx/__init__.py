@@ -82,6 +82,17 @@ class SpecStateView(C.Structure):
     _fields_ = [("rows", f32p), ("pending", f32p), ("position", u64p)]
 
 
+class NbConfig(C.Structure):
+    """struct selenite_rx_nb_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("frame", C.c_uint32), ("guard", C.c_uint32), ("max_hits", C.c_uint32),
+                ("threshold", C.c_float), ("alpha", C.c_float), ("clamp", C.c_float)]
+
+
+class NbStateView(C.Structure):
+    """struct selenite_rx_nb_state_view."""
+    _fields_ = [("level", f32p), ("blanked", u64p), ("bursts", u64p)]
+
+
 # every symbol include/selenite_rx.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "selenite_rx_init", "selenite_rx_free", "selenite_rx_set_mode", "selenite_rx_status",
@@ -103,6 +114,7 @@ ABI_SYMBOLS = [
     "selenite_rx_set_out", "selenite_rx_out_values", "selenite_rx_get_out_state", "selenite_rx_set_out_state", "selenite_rx_design_interp",
     "selenite_rx_set_spectrum", "selenite_rx_get_spectrum", "selenite_rx_spectrum_device", "selenite_rx_get_spectrum_state",
     "selenite_rx_set_spectrum_state", "selenite_rx_spectrum_twiddles", "selenite_rx_design_window",
+    "selenite_rx_set_nb", "selenite_rx_get_nb_state", "selenite_rx_set_nb_state",
 ]
 
 class TxConfig(C.Structure):
@@ -239,6 +251,10 @@ def lib():
             L.selenite_rx_set_spectrum_state.argtypes = [vp, C.POINTER(SpecStateView)]
             L.selenite_rx_spectrum_twiddles.argtypes = [f32p, C.c_uint32]
             L.selenite_rx_design_window.argtypes = [f32p, C.c_uint32, C.c_int]
+        if hasattr(L, "selenite_rx_set_nb"):                # (an older build named by SELENITE_RX_LIB lacks the noise blanker)
+            L.selenite_rx_set_nb.argtypes = [vp, C.POINTER(NbConfig)]
+            L.selenite_rx_get_nb_state.argtypes = [vp, C.POINTER(NbStateView)]
+            L.selenite_rx_set_nb_state.argtypes = [vp, C.POINTER(NbStateView)]
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -769,6 +785,49 @@ class Rx:
         rc = self.L.selenite_rx_set_spectrum_state(self.h, C.byref(v))
         if rc:
             raise RxError(rc, "selenite_rx_set_spectrum_state")
+
+    # -- impulse noise blanker (selenite_rx_set_nb) ---------------------------------------------
+    def set_nb(self, frame=64, guard=2, max_hits=8, threshold=8.0, alpha=0.125, clamp=2.0):
+        """Put the noise blanker on the raw input of every channel, in front of the NCO, or remove it (frame=None).  Clears the blanker's
+        state.  Raises RxError on a bad field; the instance is then left as it was."""
+        old, self._nb = getattr(self, "_nb", None), None
+        if frame is None:
+            rc = self.L.selenite_rx_set_nb(self.h, None)
+        else:
+            g = NbConfig()
+            g.struct_size = C.sizeof(NbConfig)
+            g.frame, g.guard, g.max_hits = int(frame), int(guard), int(max_hits)
+            g.threshold, g.alpha, g.clamp = float(threshold), float(alpha), float(clamp)
+            rc = self.L.selenite_rx_set_nb(self.h, C.byref(g))
+        if rc in (ARGUMENT_ERROR, LENGTH_ERROR):
+            self._nb = old
+        if rc:
+            raise RxError(rc, self.L.selenite_rx_error_string(None).decode() if rc in (ARGUMENT_ERROR, LENGTH_ERROR) else self.error())
+        self._nb = int(frame) if frame is not None else None
+
+    def nb_state(self):
+        """dict(level [channels] f32, blanked [channels] u64, bursts [channels] u64); drains the stream"""
+        if getattr(self, "_nb", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the noise blanker is off")
+        c = self.cfg.channels
+        a = dict(level=np.zeros(c, np.float32), blanked=np.zeros(c, np.uint64), bursts=np.zeros(c, np.uint64))
+        v = NbStateView(_fp(a["level"]), a["blanked"].ctypes.data_as(u64p), a["bursts"].ctypes.data_as(u64p))
+        rc = self.L.selenite_rx_get_nb_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_nb_state")
+        return a
+
+    def set_nb_state(self, d):
+        if getattr(self, "_nb", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the noise blanker is off")
+        a = {k: np.ascontiguousarray(d[k], np.float32 if k == "level" else np.uint64) for k in d}
+        for k in a:
+            assert a[k].shape == (self.cfg.channels,), (k, a[k].shape)
+        v = NbStateView(_fp(a["level"]) if "level" in a else None, a["blanked"].ctypes.data_as(u64p) if "blanked" in a else None,
+                        a["bursts"].ctypes.data_as(u64p) if "bursts" in a else None)
+        rc = self.L.selenite_rx_set_nb_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_set_nb_state")
 
     def close(self):
         if self.h:
