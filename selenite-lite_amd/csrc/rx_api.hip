@@ -273,17 +273,14 @@ extern "C" int selenite_rx_init(selenite_rx_instance **out, const selenite_rx_co
         INITCHK(hipHostMalloc(reinterpret_cast<void **>(&S->h_rerun_seen), sizeof(uint32_t), hipHostMallocMapped));
         *S->h_rerun_seen = 0u;
     }
-    if (cfg->arith == SELENITE_ARITH_AUTO && cfg->nd_taps >= 2 && cfg->nh_taps >= 2 &&
-        split16_template_nd((int)cfg->nd_taps, (int)cfg->decim, (int)cfg->nh_taps) > 0 && !diag_env("SELENITE_RX_NO_HIST_EXT")) {
-        // k_ssb_split16 leaves the mixed samples in front of the decimator state here (two buffers: the one a channel's state points
-        // at stays intact while the next call fills the other), for k_hist_exact
-        // (round 4: allocated by the first call that needs it -- 2 x channels x ext_len x 8 bytes, 4 KB per channel for the cfg3 chain --
-        // and released when the repair is switched off: ensure_hist_ext / selenite_rx_set_handover_repair)
-        S->ext_len = cfg->decim * ((cfg->nh_taps - 1u + 3u) & ~3u);
-    }
+    // k_ssb_split16 leaves the mixed samples in front of the decimator state in rows of ext_len samples (two buffers: the one a channel's
+    // state points at stays intact while the next call fills the other), for k_hist_exact
+    // (round 4: allocated by the first call that needs it -- 2 x channels x ext_len x 8 bytes, 4 KB per channel for the cfg3 chain --
+    // and released when the repair is switched off: ensure_hist_ext / selenite_rx_set_handover_repair)
+    if (!diag_env("SELENITE_RX_NO_HIST_EXT")) S->ext_len = hist_ext_len(*cfg);
 #undef INITCHK
     classify_coeffs(S);
-    if (plan_fused(S->cfg, S->delay_is_impulse, S->delay_index, S->hilb_odd_only, S->plan) != hipSuccess) {
+    if (plan_fused(S->cfg, S->delay_is_impulse, S->hilb_odd_only, S->plan) != hipSuccess) {
         int rc_ = fail(nullptr, SELENITE_RX_DEVICE_ERROR, "selenite_rx_init: building fused-kernel tables failed");
         free_device(S);
         delete S;
@@ -312,7 +309,7 @@ extern "C" int selenite_rx_set_mode(selenite_rx_instance *S, uint8_t mode)
         return SELENITE_RX_ARGUMENT_ERROR;          // instance stays usable in its old mode
     }
     S->cfg.mode = mode;
-    HIPCHK(S, plan_fused(S->cfg, S->delay_is_impulse, S->delay_index, S->hilb_odd_only, S->plan));
+    HIPCHK(S, plan_fused(S->cfg, S->delay_is_impulse, S->hilb_odd_only, S->plan));
     return SELENITE_RX_SUCCESS;
 }
 
@@ -324,8 +321,8 @@ extern "C" const char *selenite_rx_error_string(const selenite_rx_instance *S)
 extern "C" const char *selenite_rx_kernel_name(const selenite_rx_instance *S)
 {
     if (!S) return "";
+    if (on_ssb_fused(S)) return S->plan.name;
     if (S->force_generic) return "generic";
-    if (S->plan.kind != 0) return S->plan.name;
     if (cw_fused_ok(S->cfg, S->cfg.block)) {
         static thread_local std::string name;
         name = "k_cw_fused<" + std::to_string(S->cfg.n_biquad) + "," + std::to_string(S->cfg.block) + ">";

@@ -7,44 +7,31 @@
 
 using namespace srx;
 
-// the shared LO repeats every 256 samples and the kernel of this instance can keep it in registers
-static bool periodic_lo(const selenite_rx_instance *S)
+// the facts select() (rx_select.h) wants of a call of block_size samples on this instance
+static SelCall call_facts(const selenite_rx_instance *S, uint32_t block_size, bool q15)
 {
-    const selenite_rx_config &g = S->cfg;
-    if (!(g.nco_enable && S->steps_uniform && (S->h_step[0] & 0x00FFFFFFu) == 0 && !S->no_periodic_lo)) return false;
-    if ((g.arith == SELENITE_ARITH_SPLIT16 || g.arith == SELENITE_ARITH_AUTO) && S->plan.d_btab16 && g.nd_taps)
-        return 256u % (g.block / g.decim) == 0 && ssb_split16_periodic_lo(split16_template_nd((int)g.nd_taps, (int)g.decim, (int)g.nh_taps), (int)g.decim, (int)g.nh_taps);
-    if (g.arith == SELENITE_ARITH_AUTO) return false;      // (runs the bit-exact k_ssb_fused)
-    // k_ssb_mfma (fma arithmetic, and split16 shapes without a matrix kernel of their own): decimation by 4, 1024-sample passes
-    return g.arith != SELENITE_ARITH_CMSIS && S->plan.use_mfma && g.nd_taps && g.decim == 4;
+    SelCall c;
+    c.block_size = block_size; c.q15 = q15;
+    c.global_gain = S->cfg.agc_enable && S->cfg.agc_global;
+    c.nr = S->nr.kind != SELENITE_RX_NR_OFF;
+    c.hist_ext = S->handover_repair && S->d_hist_ext;
+    c.steps_uniform = S->steps_uniform; c.phase_uniform = S->phase_uniform; c.steps_grid256 = S->steps_grid256;
+    c.no_shared_lo = S->no_shared_lo; c.no_periodic_lo = S->no_periodic_lo;
+    c.auto_launches = S->auto_launches; c.rerun_words = S->d_rerun_flag != nullptr;
+    return c;
 }
 
-// every channel has its own LO, each of them periodic in 256 samples (all steps multiples of 2^24), and the kernel that serves
-// this instance's whole-pass calls computes one period per channel and call and keeps it in registers (NCO == 4 flavour of
-// k_ssb_split16 and of k_ssb_fused; k_ssb_mfma and k_hilb_split16 have none: per-sample NCO there)
-static bool periodic_lo_per_channel(const selenite_rx_instance *S)
-{
-    const selenite_rx_config &g = S->cfg;
-    if (!(g.nco_enable && S->steps_grid256 && !S->no_periodic_lo && S->plan.kind != 0)) return false;
-    if (256u % (g.block / g.decim) != 0) return false;                       // passes of 256 outputs only
-    const bool split = (g.arith == SELENITE_ARITH_SPLIT16 || g.arith == SELENITE_ARITH_AUTO) && S->plan.d_btab16;
-    if (split && g.nd_taps) return ssb_split16_periodic_lo(split16_template_nd((int)g.nd_taps, (int)g.decim, (int)g.nh_taps), (int)g.decim, (int)g.nh_taps);
-    if (split) return false;                                                 // k_hilb_split16: per-sample NCO (and its AUTO rerun with it)
-    const bool exact = g.arith == SELENITE_ARITH_CMSIS || g.arith == SELENITE_ARITH_AUTO;
-    return exact || !(S->plan.use_mfma && g.decim == 4);                     // k_ssb_fused; the fma arithmetic by 4 runs k_ssb_mfma
-}
-
+// the LO fields of the decision, in words (the call length does not move them)
 extern "C" const char *selenite_rx_nco_path(const selenite_rx_instance *S)
 {
     if (!S) return "";
     if (!S->cfg.nco_enable) return "off";
-    const bool fused = !S->force_generic && (S->plan.kind != 0 || cw_fused_ok(S->cfg, S->cfg.block));
-    if (!fused || !S->steps_uniform || !S->phase_uniform || S->no_shared_lo) {
-        if (fused && S->plan.kind != 0 && periodic_lo_per_channel(S))
-            return "per-channel LO, period 256 samples (arm_sin/cos_f32 once per channel and call), held in registers";
-        return "per-channel arm_sin/cos_f32 in the kernel";
-    }
-    return periodic_lo(S) ? "shared LO, period 256 samples, held in registers" : "shared LO table per call";
+    const bool ssb = on_ssb_fused(S);
+    if (!ssb && (S->force_generic || !cw_fused_ok(S->cfg, S->cfg.block))) return "per-channel arm_sin/cos_f32 in the kernel";
+    const Decision d = select(S->cfg, ssb ? S->plan.sel : SelPlan{}, call_facts(S, S->cfg.block, false));
+    if (d.nco_rx == 2) return d.lo_period ? "shared LO, period 256 samples, held in registers" : "shared LO table per call";
+    return d.lo_period ? "per-channel LO, period 256 samples (arm_sin/cos_f32 once per channel and call), held in registers"
+                       : "per-channel arm_sin/cos_f32 in the kernel";
 }
 
 // SELENITE_ARITH_AUTO on a shape with a split-precision decimator: the rows k_ssb_split16 leaves for k_hist_exact, allocated by the
@@ -105,17 +92,15 @@ bool srx::block_size_ok(selenite_rx_instance *S, uint32_t block_size, const char
 }
 
 // The one dispatcher behind every process entry point.
-// (phase_now: the common NCO phase at the first sample of this launch)
-static int run_part(selenite_rx_instance *S, ChanRange r, uint32_t phase_now, const void *src, bool src_q15, void *dst, bool dst_q15,
+// (phase_now: the common NCO phase at the first sample of this launch; d: select() for this launch)
+static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uint32_t phase_now, const void *src, bool src_q15, void *dst, bool dst_q15,
                     uint32_t block_size, Phase phase, float *ext_env, uint32_t in_stride, uint32_t out_stride)
 {
     const selenite_rx_config &g = S->cfg;
     HIPCHK(S, hipSetDevice(S->device));
-    if (phase != kPhase2 && S->plan.kind != 0 && S->plan.d_btab16 && !S->force_generic)
-        if (int rc = ensure_hist_ext(S)) return rc;
     RxParams p = make_params(S, r, block_size);
     p.in_stride = in_stride; p.out_stride = out_stride;
-    if (front_generic_lds_bytes(p) > 64 * 1024 && (S->force_generic || S->plan.kind == 0))
+    if (front_generic_lds_bytes(p) > 64 * 1024 && !on_ssb_fused(S))
         return fail(S, SELENITE_RX_LENGTH_ERROR, "filter lengths exceed the LDS budget of the generic kernel");
     const int arith = (int)g.arith;
     const int garith = arith == SELENITE_ARITH_AUTO ? SELENITE_ARITH_CMSIS : arith;      // the generic kernels: AUTO is bit-exact there
@@ -131,11 +116,11 @@ static int run_part(selenite_rx_instance *S, ChanRange r, uint32_t phase_now, co
     // int16 load performs -- and run as an f32-input call whose gain pass stores int16; round 2 left them to the generic kernels)
     // (the NLMS stage the same way: the fused kernel leaves un-scaled f32 audio, the stage runs in place on it, the AGC pass stores)
     const bool fusable = phase != kPhase2 && !S->force_generic;
-    const bool ssb_fused = fusable && S->plan.kind != 0;
+    const bool ssb_fused = fusable && on_ssb_fused(S);
     const bool cw_fused = fusable && cw_fused_ok(g, block_size) && cw_strides_ok(p.in_stride, p.out_stride);    // (wider strides: the generic kernels)
     if ((global || nr) && src_q15 && (ssb_fused || cw_fused)) {
         // int16 values of the call (block_size % 4 == 0 for every fused shape), up to the end of the last channel's block_size samples: the
-        // second part of a fused_tail_split call starts inside the rows (= p.channels * p.in_stride * 2 when the call is not split)
+        // second part of a cut call (run_chain_core) starts inside the rows (= p.channels * p.in_stride * 2 when the call is not split)
         const size_t nval = ((size_t)(p.channels - 1) * p.in_stride + block_size) * 2;
         if (nval % 8 == 0) {
             int rc = ensure(S, (void **)&S->d_conv_in, &S->conv_in_bytes, nval * sizeof(float));
@@ -168,34 +153,27 @@ static int run_part(selenite_rx_instance *S, ChanRange r, uint32_t phase_now, co
     bool env_emitted = false;      // global gain: the fused kernel wrote the per-channel block maxima
     if (ssb_fused || cw_fused) {
         RxParams pf = p;
-        if (g.nco_enable && S->steps_uniform && S->phase_uniform && !S->no_shared_lo) {
+        pf.nco = d.nco_rx; pf.lo_period = d.lo_period;
+        if (d.lo_n) {
             // one LO for all channels: computed once per call, read from L2 by every wavefront
             // the table is a pure function of (start phase, step, length): a call that starts where the table in d_lo
             // starts reuses it -- every chunk of a pipelined host call, and EVERY call when the phase advance of a call
             // is a multiple of 2^32 (an LO on the fs / 256 grid with calls of whole DSP blocks)
-            // (at least one whole period: the register-resident flavour reads LO[0 .. 255] whatever the call length)
-            const uint32_t lo_n = block_size < 256u ? 256u : block_size;
-            if (!(S->lo_valid && S->lo_phase == phase_now && S->lo_step == S->h_step[0] && S->lo_n >= lo_n)) {
+            if (!(S->lo_valid && S->lo_phase == phase_now && S->lo_step == S->h_step[0] && S->lo_n >= d.lo_n)) {
                 S->lo_valid = false;
-                int rc = ensure(S, (void **)&S->d_lo, &S->lo_bytes, (size_t)lo_n * sizeof(float2));
+                int rc = ensure(S, (void **)&S->d_lo, &S->lo_bytes, (size_t)d.lo_n * sizeof(float2));
                 if (rc) return rc;
-                HIPCHK(S, launch_lo_table(S->d_lo, S->d_sintab, phase_now, S->h_step[0], lo_n, st));
-                S->lo_valid = true; S->lo_phase = phase_now; S->lo_step = S->h_step[0]; S->lo_n = lo_n;
+                HIPCHK(S, launch_lo_table(S->d_lo, S->d_sintab, phase_now, S->h_step[0], d.lo_n, st));
+                S->lo_valid = true; S->lo_phase = phase_now; S->lo_step = S->h_step[0]; S->lo_n = d.lo_n;
             }
-            pf.nco = 2;
             pf.lo = S->d_lo;
-            // a step that is a multiple of 2^24 repeats the LO every 256 samples (channelised receivers: LO
-            // frequencies on a grid of fs / 256): k_ssb_split16 then keeps it in registers (its NCO == 3 flavour)
-            pf.lo_period = periodic_lo(S) ? 256u : 0u;
-        } else if (ssb_fused && g.nco_enable && periodic_lo_per_channel(S)) {
-            pf.lo_period = 256u;                          // pf.nco stays 1: every channel computes its own period once
         }
         if (arith == SELENITE_ARITH_AUTO && ssb_fused) {
             // the split16 kernel raises the rerun flag of the channels it guards and leaves their state alone; the bit-exact
             // kernel then recomputes the flagged channels (launch_fused)
             pf.rerun_flag = S->d_rerun_flag + r.first;
             pf.chan_list = S->d_rerun_list + 2;
-            pf.chan_count = S->d_rerun_list;              // the two counters; launch_shape picks by *rerun_par_host where it launches the prepare kernel
+            pf.chan_count = S->d_rerun_list;              // the two counters; launch_fused picks by *rerun_par_host where it launches the prepare kernel
             pf.rerun_par_host = &S->rerun_par;
             pf.rerun_seen = S->h_rerun_seen;
             pf.auto_inline = S->auto_launches == 1 ? 1u : 0u;
@@ -206,10 +184,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, uint32_t phase_now, co
         if (global || nr) {
             pf.agc = 0; fdst = audio; fq15 = false;
             pf.out_cached = 1;                            // phase 2 (and, without block maxima from the kernel, the envelope fold) reads this audio back
-            // k_ssb_split16 (16-lane DSP blocks, whole passes) leaves the block maxima of every channel behind: the
-            // envelope reduction below then folds channels x blocks floats instead of reading the audio again
-            if (!nr && ssb_fused && (arith == SELENITE_ARITH_SPLIT16 || arith == SELENITE_ARITH_AUTO) && S->plan.d_btab16 && g.nd_taps && g.decim == 4 && (g.block / g.decim) / 4 == 16 &&
-                (block_size / g.decim) % 256 == 0 && g.nco_enable && g.mode != SELENITE_MODE_AM && g.mode != SELENITE_MODE_FM) {   // the launches with the DPP block reductions (decimation by 4, 64-sample audio blocks)
+            if (d.env_part) {                             // the kernel leaves the block maxima of every channel behind: folded below
                 const size_t need = sizeof(float) * env_fold_scratch_floats(p.channels, block_size / g.block);
                 int rc = ensure(S, (void **)&S->d_env_part, &S->env_part_cap, need);
                 if (rc) return rc;
@@ -217,7 +192,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, uint32_t phase_now, co
                 env_emitted = true;
             }
         }
-        if (ssb_fused) HIPCHK(S, launch_fused(S->plan, pf, arith, src, src_q15, fdst, fq15, S->delay_index, st));
+        if (ssb_fused) HIPCHK(S, launch_fused(S->plan, pf, d, src, src_q15, fdst, fq15, S->delay_index, st));
         else HIPCHK(S, launch_cw_fused(pf, src, src_q15, fdst, fq15, st));
         if (!global && !nr) return SELENITE_RX_SUCCESS;
     }
@@ -254,28 +229,29 @@ static int run_part(selenite_rx_instance *S, ChanRange r, uint32_t phase_now, co
     return SELENITE_RX_SUCCESS;
 }
 
-// Entry of every process call.  Any call length (a whole number of DSP blocks) runs on the fused kernels; a
-// split-precision call that ends in a partial pass too short for the matrix kernel is cut in two launches on the same
-// streaming state (fused_tail_split; both parts address the caller's buffers with the full per-channel stride; in
-// SELENITE_ARITH_AUTO the tail runs in the bit-exact arithmetic, rx_fused.hip launch_shape).
+// Entry of every process call: decides once which kernel serves it (rx_select.h) and runs that.  A split-precision call that ends in a
+// partial pass too short for the matrix kernel is cut in two launches on the same streaming state, each decided as a call of its own;
+// both parts address the caller's buffers with the full per-channel stride.  The tail is shorter than a pass, which k_ssb_split16
+// takes: under SELENITE_ARITH_SPLIT16 it runs there; under SELENITE_ARITH_AUTO it is too short to leave the repair rows behind and runs
+// on the bit-exact k_ssb_fused, from a history k_hist_exact repairs first.
 static int run_chain_core(selenite_rx_instance *S, ChanRange r, uint32_t phase_now, const void *src, bool src_q15, void *dst, bool dst_q15,
                           uint32_t block_size, Phase phase, float *ext_env)
 {
     const selenite_rx_config &g = S->cfg;
     const uint32_t nout = block_size / g.decim;
-    const bool global = g.agc_enable && g.agc_global;
-    if (phase == kAll && !global && !S->force_generic && S->plan.kind != 0 && fused_tail_split(S->plan, g, block_size)) {
-        const uint32_t unit = split16_pass_out(g.block, g.decim) * g.decim, bs1 = block_size / unit * unit;
-        {
-            int rc = run_part(S, r, phase_now, src, src_q15, dst, dst_q15, bs1, kAll, nullptr, block_size, nout);
-            if (rc) return rc;
-            const size_t ein = src_q15 ? sizeof(int16_t) : sizeof(float), eout = dst_q15 ? sizeof(int16_t) : sizeof(float);
-            const char *src2 = static_cast<const char *>(src) + (size_t)bs1 * 2 * ein;
-            char *dst2 = static_cast<char *>(dst) + (size_t)(bs1 / g.decim) * eout;
-            return run_part(S, r, phase_now + bs1 * S->h_step[0], src2, src_q15, dst2, dst_q15, block_size - bs1, kAll, nullptr, block_size, nout);
-        }
-    }
-    return run_part(S, r, phase_now, src, src_q15, dst, dst_q15, block_size, phase, ext_env, block_size, nout);
+    const bool ssb = phase != kPhase2 && on_ssb_fused(S);
+    if (ssb && S->plan.sel.btab16)
+        if (int rc = ensure_hist_ext(S)) return rc;
+    SelCall c = call_facts(S, block_size, dst_q15);
+    const Decision d = select(g, ssb ? S->plan.sel : SelPlan{}, c);
+    if (!d.first) return run_part(S, r, d, phase_now, src, src_q15, dst, dst_q15, block_size, phase, ext_env, block_size, nout);
+    const uint32_t bs1 = d.first;
+    if (int rc = run_part(S, r, d, phase_now, src, src_q15, dst, dst_q15, bs1, kAll, nullptr, block_size, nout)) return rc;
+    const size_t ein = src_q15 ? sizeof(int16_t) : sizeof(float), eout = dst_q15 ? sizeof(int16_t) : sizeof(float);
+    const char *src2 = static_cast<const char *>(src) + (size_t)bs1 * 2 * ein;
+    char *dst2 = static_cast<char *>(dst) + (size_t)(bs1 / g.decim) * eout;
+    c.block_size = block_size - bs1;
+    return run_part(S, r, select(g, S->plan.sel, c), phase_now + bs1 * S->h_step[0], src2, src_q15, dst2, dst_q15, c.block_size, kAll, nullptr, block_size, nout);
 }
 
 // With an output stage the chain runs exactly as without one, into the instance's f32 audio buffer, and the stage kernel writes the caller's dst.

@@ -25,6 +25,7 @@
 // and type-III (odd-only) Hilbert taps; USB/LSB/DIG/PKT (and CW/CWR without biquads); per-channel
 // AGC with block/M in {4..256, power of two}.  Everything else runs on rx_generic.hip.
 #include "rx_fused_kernels.h"
+#include "rx_host.h"
 
 #include <cmath>
 #include <cstdio>
@@ -342,68 +343,28 @@ hipError_t launch_lo_table(float2 *lo, const float *sintab, uint32_t phase0, uin
 // ------------------------------------------------------------------------------------------
 // host side: plan + dispatch
 // ------------------------------------------------------------------------------------------
-// the instantiated shape that serves a configuration: the same decimation ratio and FIR pair, and the SHORTEST decimator that holds the
-// instance's (round 4: any 2 <= nd <= 256 runs on the fused kernels with its taps zero-padded in front; nd = 0 needs nd = 0)
-int fused_template_nd(int nd, int m, int nh)
+// The operand of a split-precision kernel: KS k-steps of a banded-Toeplitz B[k][n] = c[k - stride n] (0 outside the nc taps), scaled by
+// 2^SC (largest |tap| lands in [2^14, 2^15)) and split into f16 hi + lo; fragment of lane l at k-step kk: 8 halfs
+// B[k = 32kk + 8(l>>4) + j][n = l&15]
+static hipError_t upload_split16(FusedPlan &plan, int KS, int stride, const float *c, int nc)
 {
-    int best = -1;
-#define X(ND_, M_, NH_, ID_) \
-    if (m == M_ && nh == NH_ && (nd == 0 ? ND_ == 0 : (ND_ >= nd && nd >= 2)) && (best < 0 || ND_ < best)) best = ND_;
-    SRX_SHAPES(X)
-#undef X
-    return best;
-}
-// ... and the shortest split-precision decimator (k_ssb_split16 wants an even tap count: its rows for k_hist_exact are pair-aligned)
-int split16_template_nd(int nd, int m, int nh)
-{
-    int best = -1;
-    if (nd < 2 || (nd & 1)) return -1;
-    if (m == 8) m = 4;                                    // decimation by 8 runs on the by-4 Toeplitz product, every second output kept (FusedArgs::dec2)
-#define X(ND_, M_, NH_) if (m == M_ && nh == NH_ && ND_ >= nd && (best < 0 || ND_ < best)) best = ND_;
-    SRX_SPLIT16_SHAPES(X)
-#undef X
-    return best;
-}
-template <int ND, int M, int NH>
-static bool shape_is(const selenite_rx_config &g)
-{
-    return fused_template_nd((int)g.nd_taps, (int)g.decim, (int)g.nh_taps) == ND && (int)g.decim == M && (int)g.nh_taps == NH;
-}
-
-// SELENITE_ARITH_SPLIT16: the Toeplitz operand of k_ssb_split16<ND, M, NH> -- ND the kernel's decimator length, which may exceed the
-// instance's (split16_template_nd): taps zero-padded in front, scaled by 2^SC (largest |tap| lands in [2^14, 2^15)), split into f16
-// hi + lo; fragment of lane l at k-step kk: 8 halfs B[k = 32kk + 8(l>>4) + j][n = l&15]
-template <int ND, int M, int NH>
-static hipError_t build_split16_table(const selenite_rx_config &g, FusedPlan &plan)
-{
-    using G = Geo<ND, M, NH>;
-    using GS = GeoS<2, ND, M, NH>;
-    const int ndr = (int)g.nd_taps, Fr = G::HQ4 * M + 1 - ndr;
-    std::vector<float> cq((size_t)G::NCQ, 0.0f);
-    for (int k = 0; k < ndr; ++k) cq[(size_t)k + Fr] = g.dec_coeffs[k];
     float cmax = 0.0f;
-    for (int k = 0; k < ndr; ++k) cmax = std::fmax(cmax, std::fabs(g.dec_coeffs[k]));
+    for (int k = 0; k < nc; ++k) cmax = std::fmax(cmax, std::fabs(c[k]));
     int ex = 0;
     if (cmax > 0.0f) std::frexp(cmax, &ex);                       // cmax = m * 2^ex, m in [0.5, 1)
     const int SC = 15 - ex;                                         // largest |tap| * 2^SC in [2^14, 2^15)
-    std::vector<_Float16> b16((size_t)GS::KS * 2 * 64 * 8, (_Float16)0.0f);
-    for (int kk = 0; kk < GS::KS; ++kk)
+    std::vector<_Float16> b16((size_t)KS * 2 * 64 * 8, (_Float16)0.0f);
+    for (int kk = 0; kk < KS; ++kk)
         for (int l = 0; l < 64; ++l)
             for (int j = 0; j < 8; ++j) {
-                const int idx = 32 * kk + 8 * (l >> 4) + j - M * (l & 15);      // B[k][n] = cq[k - M n]
-                float cv = 0.0f;
-                if (idx >= 0 && idx < G::NCQ) cv = std::ldexp(cq[idx], SC);
+                const int idx = 32 * kk + 8 * (l >> 4) + j - stride * (l & 15);
+                const float cv = idx >= 0 && idx < nc ? std::ldexp(c[idx], SC) : 0.0f;
                 const _Float16 hi = (_Float16)cv;
-                const _Float16 lo = (_Float16)(cv - (float)hi);
                 b16[(((size_t)2 * kk + 0) * 64 + l) * 8 + j] = hi;
-                b16[(((size_t)2 * kk + 1) * 64 + l) * 8 + j] = lo;
+                b16[(((size_t)2 * kk + 1) * 64 + l) * 8 + j] = (_Float16)(cv - (float)hi);
             }
-    hipError_t e = hipMalloc(&plan.d_btab16, b16.size() * sizeof(_Float16));
-    if (e != hipSuccess) return e;
-    e = hipMemcpy(plan.d_btab16, b16.data(), b16.size() * sizeof(_Float16), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return e;
     plan.split_sc = SC;
-    return hipSuccess;
+    return dev_upload(reinterpret_cast<_Float16 **>(&plan.d_btab16), b16.data(), b16.size());
 }
 
 template <int ND, int M, int NH>
@@ -415,11 +376,7 @@ static hipError_t build_tables(const selenite_rx_config &g, FusedPlan &plan, boo
         std::vector<float> cq((size_t)64 * G::NCR, 0.0f);
         const int ndr = (int)g.nd_taps, Fr = G::HQ4 * M + 1 - ndr;      // the instance's taps, zero-padded in front up to the kernel's length
         for (int k = 0; k < ndr; ++k) cq[(size_t)k + Fr] = g.dec_coeffs[k];
-        hipError_t e = hipMalloc((void **)&plan.d_cq, cq.size() * sizeof(float));
-        if (e != hipSuccess) return e;
-        e = hipMemcpy(plan.d_cq, cq.data(), cq.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return e;
-        if (dense) return hipSuccess;                                 // (the dense flavour runs on k_ssb_fused only: no matrix operands)
+        if (hipError_t e = dev_upload(&plan.d_cq, cq.data(), cq.size()); e != hipSuccess || dense) return e;      // (the dense flavour runs on k_ssb_fused only: no matrix operands)
         if constexpr (M == 4) {
             // Toeplitz operand of k_ssb_mfma: btab[ks][lane] = cq[k - 4n], k = 4ks + (lane>>4), n = lane&15
             using GM = GeoM<ND, M, NH>;
@@ -429,50 +386,26 @@ static hipError_t build_tables(const selenite_rx_config &g, FusedPlan &plan, boo
                     const int idx = 4 * ks + (l >> 4) - 4 * (l & 15);
                     if (idx >= 0 && idx < G::NCQ) bt[(size_t)64 * ks + l] = cq[idx];
                 }
-            e = hipMalloc((void **)&plan.d_btab, bt.size() * sizeof(float));
-            if (e != hipSuccess) return e;
-            e = hipMemcpy(plan.d_btab, bt.data(), bt.size() * sizeof(float), hipMemcpyHostToDevice);
-            if (e != hipSuccess) return e;
+            if (hipError_t e = dev_upload(&plan.d_btab, bt.data(), bt.size()); e != hipSuccess) return e;
         }
-        if (NH > 0) {                                                 // the split-precision decimator's operand, for ITS shape
-            const int nds = split16_template_nd(ndr, M, NH);
-            constexpr int MT = M == 8 ? 4 : M;                        // (by 8: the by-4 product's table)
-#define X(ND_, M_, NH_) if (nds == ND_ && MT == M_ && NH == NH_) return build_split16_table<ND_, M_, NH_>(g, plan);
-            SRX_SPLIT16_SHAPES(X)
+        // SELENITE_ARITH_SPLIT16: the operand of k_ssb_split16<nds, M, NH> -- nds the kernel's decimator length, which may exceed the
+        // instance's (split16_template_nd): taps zero-padded in front; by 8: the by-4 product's table
+        constexpr int MT = M == 8 ? 4 : M;
+#define X(ND_, M_, NH_) \
+        if (plan.sel.nds == ND_ && MT == M_ && NH == NH_) { \
+            using GT = Geo<ND_, M_, NH_>; \
+            std::vector<float> ct((size_t)GT::NCQ, 0.0f); \
+            for (int k = 0; k < ndr; ++k) ct[(size_t)k + GT::HQ4 * M_ + 1 - ndr] = g.dec_coeffs[k]; \
+            return upload_split16(plan, GeoS<2, ND_, M_, NH_>::KS, M_, ct.data(), GT::NCQ); \
+        }
+        SRX_SPLIT16_SHAPES(X)
 #undef X
-        }
         return hipSuccess;
     }
-    if constexpr (ND == 0 && M == 1 && NH > 0) {
-        // k_hilb_split16: Hilbert taps scaled by 2^SC, f16 hi + lo; fragment of lane l at k-step kk:
-        // 8 halfs B[k = 32kk + 8(l>>4) + j][m = l&15] = h[k - m]
-        using GH = GeoH<NH>;
-        float cmax = 0.0f;
-        for (int k = 0; k < NH; ++k) cmax = std::fmax(cmax, std::fabs(g.hilb_coeffs[k]));
-        int ex = 0;
-        if (cmax > 0.0f) std::frexp(cmax, &ex);
-        const int SC = 15 - ex;
-        std::vector<_Float16> b16((size_t)GH::KS * 2 * 64 * 8, (_Float16)0.0f);
-        for (int kk = 0; kk < GH::KS; ++kk)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int idx = 32 * kk + 8 * (l >> 4) + j - (l & 15);
-                    float cv = 0.0f;
-                    if (idx >= 0 && idx < NH) cv = std::ldexp(g.hilb_coeffs[idx], SC);
-                    const _Float16 hi = (_Float16)cv;
-                    const _Float16 lo = (_Float16)(cv - (float)hi);
-                    b16[(((size_t)2 * kk + 0) * 64 + l) * 8 + j] = hi;
-                    b16[(((size_t)2 * kk + 1) * 64 + l) * 8 + j] = lo;
-                }
-        hipError_t e = hipMalloc(&plan.d_btab16, b16.size() * sizeof(_Float16));
-        if (e != hipSuccess) return e;
-        e = hipMemcpy(plan.d_btab16, b16.data(), b16.size() * sizeof(_Float16), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return e;
-        plan.split_sc = SC;
-    }
+    // k_hilb_split16: the Hilbert taps, B[k][m] = h[k - m]
+    if constexpr (ND == 0 && M == 1 && NH > 0) return upload_split16(plan, GeoH<NH>::KS, 1, g.hilb_coeffs, NH);
     return hipSuccess;
 }
-
 
 template <int ND, int M, int NH, typename TIn, typename TOut>
 static hipError_t launch_mfma(const RxParams &p, const FusedArgs &fa, const float *btab, const void *src, void *dst,
@@ -481,7 +414,8 @@ static hipError_t launch_mfma(const RxParams &p, const FusedArgs &fa, const floa
     using GM = GeoM<ND, M, NH>;
     constexpr size_t lds = (size_t)kMfmaWaves * GM::total * sizeof(float);
     static_assert(lds <= 160 * 1024, "k_ssb_mfma LDS image");
-    const uint32_t nco = (p.nco == 2 && p.lo_period == 256 && Geo<ND, M, NH>::T % 256 == 0) ? 3u : p.nco;     // periodic LO: in registers
+    const uint32_t nco = fa.nco;                                      // (3: periodic shared LO, in registers)
+    if (nco > 3u) return hipErrorNotSupported;
     auto k = fa.am ? (nco == 3 ? k_ssb_mfma<3, ND, M, NH, TIn, TOut, 1> : nco == 2 ? k_ssb_mfma<2, ND, M, NH, TIn, TOut, 1>
                          : (nco == 1 ? k_ssb_mfma<1, ND, M, NH, TIn, TOut, 1> : k_ssb_mfma<0, ND, M, NH, TIn, TOut, 1>))
                    : (nco == 3 ? k_ssb_mfma<3, ND, M, NH, TIn, TOut, 0> : nco == 2 ? k_ssb_mfma<2, ND, M, NH, TIn, TOut, 0>
@@ -490,17 +424,8 @@ static hipError_t launch_mfma(const RxParams &p, const FusedArgs &fa, const floa
                                        (int)lds);
     if (e != hipSuccess) return e;
     // persistent grid: as many workgroups as the device keeps resident (SELENITE_RX_MFMA_GRID=0: one per channel)
-    static int resident = 0;                // per shape and slot format; the NCO / AM flavours share the resource footprint closely enough
-    if (resident == 0) {
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 64 * kMfmaWaves, lds) == hipSuccess && per_cu > 0 &&
-            hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            resident = per_cu * prop.multiProcessorCount;
-        else
-            resident = -1;
-        if (const char *ge = diag_env("SELENITE_RX_MFMA_GRID")) resident = std::atoi(ge) > 0 ? std::atoi(ge) : -1;
-    }
+    // (per shape and slot format; the NCO / AM flavours share the resource footprint closely enough)
+    static const int resident = resident_workgroups(k, 64 * kMfmaWaves, lds, "SELENITE_RX_MFMA_GRID");
     uint32_t grid = p.channels / kMfmaWaves;
     if (resident > 0 && (uint32_t)resident < grid) grid = (uint32_t)resident;
     hipLaunchKernelGGL(k, dim3(grid), dim3(64 * kMfmaWaves), lds, st, p, fa, btab,
@@ -509,163 +434,74 @@ static hipError_t launch_mfma(const RxParams &p, const FusedArgs &fa, const floa
 }
 
 template <int ND, int M, int NH>
-static hipError_t launch_shape(const RxParams &p, const FusedArgs &fa, const FusedPlan &plan, int arith,
-                               const void *src, bool src_q15, void *dst, bool dst_q15, hipStream_t st)
+static hipError_t launch_shape(const RxParams &p, const FusedArgs &fa, const FusedPlan &plan, const Decision &d,
+                               const void *src, bool q15, void *dst, hipStream_t st)
 {
-    if (src_q15 != dst_q15) return hipErrorNotSupported;
-    const bool auto_ = arith == SELENITE_ARITH_AUTO;
-    // FM: the discriminator divides by |z|, so no parity bar holds on a raw split product (SPLIT16 runs FM as FMA).  AUTO (round 4) has
-    // the guard for it: a block is guarded when min|z| x max|audio| < ratio x pass maximum, its channel recomputed by the bit-exact kernel
-    // -- on the decimating shapes (k_ssb_split16); the no-decimator shapes keep the bit-exact kernel (their FIR pair is not on the matrix pipe in FM)
-    const bool fm = fa.am == 2u;
-    const bool split = (arith == SELENITE_ARITH_SPLIT16 || auto_) && !(fm && !(auto_ && ND > 0));
-    // SELENITE_ARITH_AUTO, second launch: the bit-exact kernel over the channels whose rerun flag the split16 kernel raised
-    // (their streaming state is still the pre-call state; audio and state are recomputed in the CMSIS arithmetic)
-    auto rerun = [&]() -> hipError_t {
-        RxParams p2 = p;
-        p2.chan_flags = p.rerun_flag;
-        p2.rerun_flag = nullptr;                      // (guard_ch / guard_calls stay: the rerun pass counts for the channels it HOLDS, which the matrix kernel skipped)
-        if (p.rerun_par_host) {                       // the dense list of this call: counted in one of two alternating counters (rx_internal.h)
-            const uint32_t par = *p.rerun_par_host & 1u;
-            p2.chan_count = p.chan_count + par;
-            p2.chan_count_next = p.chan_count + (par ^ 1u);
-            *p.rerun_par_host = par ^ 1u;
-        }
-        // (channels the call before left on the matrix kernel: their Hilbert-pair history first, in exact arithmetic -- rx_generic.hip)
-        if (hipError_t e = launch_hist_exact(p2, false, st); e != hipSuccess) return e;
-        return launch_exact(ND, M, NH, src_q15, p2, fa, src, dst, st);            // rx_fused_exact.hip
-    };
-    // what the matrix kernels take: DSP blocks that divide the 256-output pass; whole passes (k_ssb_mfma, k_hilb_split16), or a
-    // partial last pass that holds a whole decimator history (k_ssb_split16).  Everything else -- short calls, the firmware's
-    // 96-frame blocks -- runs on k_ssb_fused, whose passes have variable length.
-    const bool whole = fa.pass_out == 256 && p.nout % 256 == 0;
-    const int nds = ND > 0 ? split16_template_nd((int)p.nd, M, NH) : -1;               // the split-precision kernel's decimator length (>= the instance's), or -1
-    const uint32_t kHS = nds > 0 ? (uint32_t)(((((nds - 1 + M - 1) / M) + 3) & ~3) * M) : 0u;      // GeoS::HS: decimator history in the image
-    // k_ssb_split16 also takes passes of fewer than 256 outputs when they are whole 16-output tiles (240 for the firmware's
-    // 96-frame blocks by 4, 192 for its 96-sample audio blocks): its run-time DSP-block flavour advances by pass_out * M samples
-    // (decimation by 8, round 4 late: the by-4 kernel with every second output kept -- passes of at most 128 outputs = 1024 inputs)
-    FusedArgs fa16 = fa;
-    if constexpr (M == 8) {
-        fa16.pass_out = split16_pass_out(p.block, p.decim);
-        // (which half: the tile's output j ends at input sample 4 j of the pass in this kernel's bookkeeping, a by-8 output n at 8 n -- the
-        // even ones; SELENITE_RX_DEC2_PARITY=2 selects the odd ones: a diagnostic that shows the tests notice)
-        // (only the value 2 is taken, and said so on stderr: anything else keeps the chain's outputs)
-        static const uint32_t par = [] {
-            const char *e = diag_env("SELENITE_RX_DEC2_PARITY");
-            if (e && e[0] == '2' && e[1] == 0) { fprintf(stderr, "selenite_rx: SELENITE_RX_DEC2_PARITY=2 -- decimation by 8 keeps the ODD by-4 outputs (diagnostic, wrong audio)\n"); return 2u; }
-            return 1u;
-        }();
-        fa16.dec2 = par;
+    // every channel the call before left on the matrix kernel: its Hilbert-pair history first, in exact arithmetic (rx_generic.hip)
+    if (d.repair_all) {
+        RxParams p3 = p;
+        p3.chan_flags = p.rerun_flag;
+        p3.chan_list = nullptr; p3.chan_count_next = nullptr;
+        if (hipError_t e = launch_hist_exact(p3, true, st); e != hipSuccess) return e;
     }
-    const uint32_t tq = fa16.pass_out * M;
-    // (a last pass shorter than the decimator history: only as a call of its own -- fused_tail_split cuts it off)
-    const bool split_ok = split16_pass_ok(fa16.pass_out) && (p.block_size % tq == 0 || p.block_size % tq >= kHS || p.block_size < tq);
-    // SELENITE_ARITH_AUTO (round 4: "handover_blocks == 0 by construction"): the matrix kernel only takes calls long enough to leave the
-    // mixed samples in front of the decimator state behind (hist_ext: nd - 1 + M HH4 - 1 samples) -- every state it leaves can then be
-    // repaired by k_hist_exact.  Shorter calls (the firmware's literal one-slot callback, a tail cut off by fused_tail_split) run on the
-    // bit-exact kernel, from a history repaired first (below): they are state-traffic bound either way.  With the repair switched
-    // off (a diagnostic: selenite_rx_set_handover_repair) nothing is kept and such calls stay on the matrix kernel, counted.
-    const bool auto_ok = !auto_ || p.hist_ext == nullptr || p.block_size + 1u >= (uint32_t)(ND > 0 ? p.nd - 1 : 0) + p.ext_len;
-    if constexpr (ND > 0 && (M == 4 || M == 2 || M == 8) && NH > 0) {
-        if (split && plan.d_btab16 && split_ok && auto_ok) {
-            if (auto_ && fa.am == 1u && p.rerun_flag) {
-                // AM neither reads nor moves the Hilbert-pair history while the decimator state moves on: the samples kept in front of
-                // that state belong to the history for the last time NOW -- repair every channel that has them, before the AM call
-                RxParams p3 = p;
-                p3.chan_flags = p.rerun_flag;
-                p3.chan_list = nullptr; p3.chan_count_next = nullptr;
-                if (hipError_t e = launch_hist_exact(p3, true, st); e != hipSuccess) return e;
-            }
-            if (auto_ && p.rerun_flag && p.form_host) *p.form_host = 3u;
-            hipError_t e = launch_ssb_split16(nds, M == 8 ? 4 : M, NH, p, fa16, src, src_q15, dst, st);     // rx_split16.hip
-            if (e == hipSuccess && auto_ && p.rerun_flag) e = rerun();
-            return e;
-        }
-    }
-    if constexpr (ND == 0 && M == 1 && NH > 0) {
-        // k_hilb_split16: whole passes of the largest whole number of DSP blocks in 256 (256 itself, or e.g. 192: BASELINE cfg2's
-        // literal 48 000 samples are 250 blocks of 192); whole 4-sample lanes per block
-        const bool hilb_ok = fa.pass_out != 0;                        // (any call length: the last pass may be partial, round 4 late)
-        if (split && plan.d_btab16 && hilb_ok) {
-            FusedArgs fah = fa;
-            const bool inl = auto_ && p.rerun_flag && p.auto_inline && !fa.am;     // (every SSB instantiation of k_hilb_split16 carries the exact body)
-            fah.inl = inl ? 1u : 0u;
-            if (auto_ && p.rerun_flag && p.form_host) *p.form_host = inl ? 1u : 3u;
-            hipError_t e = launch_hilb_split16(NH, p, fah, src, src_q15, dst, st);           // rx_split16.hip
-            if (e == hipSuccess && auto_ && p.rerun_flag && !inl) e = rerun();
-            return e;
-        }
-    }
-    if (auto_) {                                  // no split-precision kernel for this launch: the bit-exact one, on every channel --
-        arith = SELENITE_ARITH_CMSIS;             // from a Hilbert-pair history in exact arithmetic where the call before left the samples for it
-        if (p.rerun_flag) {
-            RxParams p3 = p;
-            p3.chan_flags = p.rerun_flag;
-            p3.chan_list = nullptr; p3.chan_count_next = nullptr;
-            if (hipError_t e = launch_hist_exact(p3, true, st); e != hipSuccess) return e;
-        }
-    }
-    if constexpr (ND > 0 && M == 4) {
+    if (d.auto_form && p.form_host) *p.form_host = d.auto_form;
+    hipError_t e = hipErrorNotSupported;              // (a family this shape has no instantiation of: select() never names one)
+    switch (d.family) {
+    case kSplit16:
+        if constexpr (ND > 0 && NH > 0) e = launch_ssb_split16(plan.sel.nds, M == 8 ? 4 : M, NH, p, fa, src, q15, dst, st);      // rx_split16.hip
+        break;
+    case kHilb16:
+        if constexpr (ND == 0 && M == 1 && NH > 0) e = launch_hilb_split16(NH, p, fa, src, q15, dst, st);                       // rx_split16.hip
+        break;
+    case kMfma:
         static_assert(kMfmaWaves == 1, "one channel per workgroup: any channel count launches (plan.name says k_ssb_mfma)");
-        if (arith != SELENITE_ARITH_CMSIS && plan.use_mfma && whole) {
-            if (src_q15) return launch_mfma<ND, M, NH, int16_t, int16_t>(p, fa, plan.d_btab, src, dst, st);
-            return launch_mfma<ND, M, NH, float, float>(p, fa, plan.d_btab, src, dst, st);
-        }
+        if constexpr (ND > 0 && M == 4)
+            e = q15 ? launch_mfma<ND, M, NH, int16_t, int16_t>(p, fa, plan.d_btab, src, dst, st)
+                    : launch_mfma<ND, M, NH, float, float>(p, fa, plan.d_btab, src, dst, st);
+        break;
+    case kFusedFma:
+        e = q15 ? launch_one<1, ND, M, NH, int16_t, int16_t>(p, fa, src, dst, st) : launch_one<1, ND, M, NH, float, float>(p, fa, src, dst, st);
+        break;
+    case kFusedExact:
+        e = launch_exact(ND, M, NH, q15, p, fa, src, dst, st);                    // rx_fused_exact.hip
+        break;
+    default: break;
     }
-    if (arith != SELENITE_ARITH_CMSIS) {
-        if (src_q15) return launch_one<1, ND, M, NH, int16_t, int16_t>(p, fa, src, dst, st);
-        return launch_one<1, ND, M, NH, float, float>(p, fa, src, dst, st);
+    if (e != hipSuccess || d.auto_form != 3u) return e;
+    // SELENITE_ARITH_AUTO, the launches behind the matrix kernel: the bit-exact kernel over the channels whose rerun flag it raised
+    // (their streaming state is still the pre-call state; audio and state are recomputed in the CMSIS arithmetic)
+    RxParams p2 = p;
+    p2.chan_flags = p.rerun_flag;
+    p2.rerun_flag = nullptr;                          // (guard_ch / guard_calls stay: the rerun pass counts for the channels it HOLDS, which the matrix kernel skipped)
+    if (p.rerun_par_host) {                           // the dense list of this call: counted in one of two alternating counters (rx_internal.h)
+        const uint32_t par = *p.rerun_par_host & 1u;
+        p2.chan_count = p.chan_count + par;
+        p2.chan_count_next = p.chan_count + (par ^ 1u);
+        *p.rerun_par_host = par ^ 1u;
     }
-    return launch_exact(ND, M, NH, src_q15, p, fa, src, dst, st);                 // rx_fused_exact.hip
+    FusedArgs fa2 = fa;                               // k_ssb_fused's own pass and NCO flavour
+    fa2.pass_out = fused_pass_out(p.block, p.decim); fa2.dec2 = 0u; fa2.nco = d.nco_rerun;
+    // (channels the call before left on the matrix kernel: their Hilbert-pair history first, in exact arithmetic -- rx_generic.hip)
+    if (hipError_t e2 = launch_hist_exact(p2, false, st); e2 != hipSuccess) return e2;
+    return launch_exact(ND, M, NH, q15, p2, fa2, src, dst, st);                   // rx_fused_exact.hip
 }
 
-
-static bool fused_mode_ok(const selenite_rx_config &g)
+hipError_t plan_fused(const selenite_rx_config &g, bool delay_is_impulse, bool hilb_odd_only, FusedPlan &plan)
 {
-    const uint32_t m = g.mode;
-    const bool ssb = m == SELENITE_MODE_USB || m == SELENITE_MODE_LSB || m == SELENITE_MODE_DIG || m == SELENITE_MODE_PKT;
-    const bool cw_plain = mode_is_cw(m) && g.n_biquad == 0;
-    return ssb || cw_plain || m == SELENITE_MODE_AM || m == SELENITE_MODE_FM;
-}
-
-hipError_t plan_fused(const selenite_rx_config &g, bool delay_is_impulse, int delay_index, bool hilb_odd_only,
-                      FusedPlan &plan)
-{
-    (void)delay_index;
-    plan.kind = 0;
-    plan.dense = false;
+    SelPlan &sel = plan.sel;
     plan.name = "generic";
-    if (!fused_mode_ok(g) || !g.nh_taps) return hipSuccess;
-    // DSP blocks of 4 .. 256 audio samples, four per lane; a power of two divides the 256-output pass, anything else (the
-    // firmware's 96 frames: 24 or 96 audio samples) runs with passes of the largest whole number of blocks (k_ssb_fused)
-    const uint32_t na = g.block / g.decim;
-    if (na < 4 || na > 256 || na % 4 != 0) return hipSuccess;
-    int kind = 0;
-    const char *name = nullptr;
-    if (delay_is_impulse && hilb_odd_only) {
-#define X(ND_, M_, NH_, ID_) \
-    if (shape_is<ND_, M_, NH_>(g)) { kind = ID_; name = "k_ssb_fused<" #ND_ "," #M_ "," #NH_ ">"; }
-    SRX_SHAPES(X)
-#undef X
-    }
-    if (!kind) {
-        // Round 4 (VERDICT r3 missing 4): anything else with a FIR pair of up to 127 taps -- dense Hilbert taps, a delay FIR that is not a
-        // unit impulse, a tap count without an instantiation of its own -- runs on the DENSE flavour of k_ssb_fused (both rails filtered
-        // with their own taps from LDS, taps zero-padded in front) instead of the generic kernels: bit-exact in the CMSIS / fma
-        // arithmetic; SPLIT16 runs as fma and AUTO as CMSIS there (no matrix kernel for a dense pair).
-        if (g.nh_taps > 127) return hipSuccess;
-        int nds = -1;
-#define X(ND_, M_, NH_, ID_) \
-        if ((int)g.decim == M_ && ((int)g.nd_taps == 0 ? ND_ == 0 : (ND_ >= (int)g.nd_taps && (int)g.nd_taps >= 2)) && (nds < 0 || ND_ < nds)) { nds = ND_; kind = ID_; }
+    sel = plan_shape(g, delay_is_impulse, hilb_odd_only);
+    const int kind = sel.kind;
+    if (!kind) return hipSuccess;
+    sel.kind = 0;                                     // (until its tables stand)
+    if (!plan.tables_built) {
+        hipError_t e = hipSuccess;
+#define X(ND_, M_, NH_, ID_) if (kind == ID_) e = build_tables<ND_, M_, NH_>(g, plan, sel.dense);
+        SRX_SHAPES(X)
         SRX_DENSE_SHAPES(X)
 #undef X
-        if (!kind) return hipSuccess;
-        if (!plan.tables_built) {
-            hipError_t e = hipSuccess;
-#define X(ND_, M_, NH_, ID_) if (kind == ID_) e = build_tables<ND_, M_, NH_>(g, plan, true);
-            SRX_DENSE_SHAPES(X)
-#undef X
-            if (e != hipSuccess) return e;
+        if (e != hipSuccess) return e;
+        if (sel.dense) {
             // the pair's tap tables: padded tap k' = k + (127 - nh) at index k' + FH + 3 (FH = 2 for the 127-tap geometry)
             constexpr int NHT = 127, LEN = DenseTab<NHT>::LEN, FH = ((NHT - 1 + 3) & ~3) - (NHT - 1);
             std::vector<float> pt((size_t)2 * LEN, 0.0f);
@@ -674,100 +510,58 @@ hipError_t plan_fused(const selenite_rx_config &g, bool delay_is_impulse, int de
                 pt[(size_t)k + pad + FH + 3] = g.delay_coeffs[k];
                 pt[(size_t)LEN + k + pad + FH + 3] = g.hilb_coeffs[k];
             }
-            e = hipMalloc((void **)&plan.d_ptab, pt.size() * sizeof(float));
-            if (e != hipSuccess) return e;
-            e = hipMemcpy(plan.d_ptab, pt.data(), pt.size() * sizeof(float), hipMemcpyHostToDevice);
-            if (e != hipSuccess) return e;
+            if ((e = dev_upload(&plan.d_ptab, pt.data(), pt.size())) != hipSuccess) return e;
             plan.dense_t0 = (uint32_t)((pad + FH - 3) > 0 ? (pad + FH - 3) / 4 : 0);
-            plan.tables_built = true;
         }
-        plan.kind = kind;
-        plan.dense = true;
-        plan.dense_delay_impulse = delay_is_impulse;     // the I rail stays one LDS read per output (0.0f + 1.0f * x), only the Hilbert FIR is dense
-        plan.use_mfma = false;
-        plan.name_buf = "k_ssb_fused<" + std::to_string(g.nd_taps) + "," + std::to_string(g.decim) + "," + std::to_string(g.nh_taps) + "> (dense FIR pair)";
-        plan.name = plan.name_buf.c_str();
-        return hipSuccess;
-    }
-    if (!plan.tables_built) {
-        hipError_t e = hipSuccess;
-#define X(ND_, M_, NH_, ID_) if (kind == ID_) e = build_tables<ND_, M_, NH_>(g, plan);
-        SRX_SHAPES(X)
-#undef X
-        if (e != hipSuccess) return e;
         plan.tables_built = true;
     }
-    plan.kind = kind;
+    // (plan_shape says which operands a shape comes with; build_tables built them)
+    if (sel.btab16 != (plan.d_btab16 != nullptr) || sel.mfma != (plan.d_btab != nullptr)) return hipErrorUnknown;
     const char *nm = diag_env("SELENITE_RX_NO_MFMA");
-    plan.use_mfma = plan.d_btab != nullptr && !(nm && nm[0] == '1');
-    const std::string shape = "<" + std::to_string(g.nd_taps) + "," + std::to_string(g.decim) + "," + std::to_string(g.nh_taps) + ">";
-    plan.name_buf = "k_ssb_fused" + shape;
-    (void)name;
-    if (plan.use_mfma && g.arith != SELENITE_ARITH_CMSIS) plan.name_buf = "k_ssb_mfma" + shape;     // split16 without a matrix kernel of its own runs as fma
-    if (g.arith == SELENITE_ARITH_AUTO) plan.name_buf = "k_ssb_fused" + shape;                      // without a matrix kernel of its own: bit-exact
-    const bool split_pass = g.nd_taps ? split16_pass_ok(split16_pass_out(g.block, g.decim)) : true;      // (k_hilb_split16 takes any pass of whole 4-sample lanes; by 8: passes of at most 128 outputs)
-    if (256 % na != 0) plan.name_buf = "k_ssb_fused" + shape;                                        // DSP blocks that do not divide a pass: variable-length passes
-    if (split_pass && plan.d_btab16 && (g.arith == SELENITE_ARITH_SPLIT16 || g.arith == SELENITE_ARITH_AUTO)) {
-        const char *tail = g.arith == SELENITE_ARITH_AUTO ? "+exact rerun of guarded channels" : "";
-        if (g.nd_taps) plan.name_buf = "k_ssb_split16" + shape + tail;
-        else plan.name_buf = "k_hilb_split16<" + std::to_string(g.nh_taps) + ">" + tail;
-    }
-    if (g.mode == SELENITE_MODE_FM && !(g.arith == SELENITE_ARITH_AUTO && g.nd_taps && plan.name_buf.rfind("k_ssb_split16", 0) == 0)) {
-        // FM: the exact / fma kernels (AUTO on a decimating shape with a matrix kernel keeps it: guarded on min|z|, round 4)
-        const bool fma = g.arith == SELENITE_ARITH_FMA || g.arith == SELENITE_ARITH_SPLIT16;
-        plan.name_buf = (fma && plan.use_mfma && g.nd_taps && g.decim == 4 ? "k_ssb_mfma" : "k_ssb_fused") + shape;
-    }
+    if (nm && nm[0] == '1') sel.mfma = false;
+    sel.kind = kind;
+    plan.dense_delay_impulse = sel.dense && delay_is_impulse;     // the I rail stays one LDS read per output (0.0f + 1.0f * x), only the Hilbert FIR is dense
+    // the name: what serves a call of whole passes, long enough for every kernel to accept it (rx_select.h: whole_pass_call says which)
+    plan.name_buf = kernel_name(g, select(g, sel, whole_pass_call(g, sel)));
     plan.name = plan.name_buf.c_str();
     return hipSuccess;
 }
 
 void free_fused(FusedPlan &plan)
 {
-    if (plan.d_cq) (void)hipFree(plan.d_cq);
-    if (plan.d_btab) (void)hipFree(plan.d_btab);
-    if (plan.d_btab16) (void)hipFree(plan.d_btab16);
-    if (plan.d_ptab) (void)hipFree(plan.d_ptab);
-    plan.d_ptab = nullptr;
-    plan.dense = false;
-    plan.d_btab16 = nullptr;
-    plan.d_cq = nullptr;
-    plan.d_btab = nullptr;
+    dev_free(plan.d_cq, plan.d_btab, plan.d_btab16, plan.d_ptab);
     plan.tables_built = false;
-    plan.kind = 0;
+    plan.sel = SelPlan{};
 }
 
-bool fused_tail_split(const FusedPlan &plan, const selenite_rx_config &g, uint32_t block_size)
-{
-    // Every call length (a whole number of DSP blocks) runs on the fused kernels since round 3 (k_ssb_fused: variable-length
-    // passes).  One case is better served in two launches: a split-precision instance whose call ends in a partial pass too
-    // short for k_ssb_split16 (it wants a whole decimator history in it; only DSP blocks shorter than that history get there):
-    // the whole passes stay on the matrix kernel, the tail goes to k_ssb_fused (SELENITE_ARITH_SPLIT16: its fma arithmetic;
-    // SELENITE_ARITH_AUTO: the bit-exact arithmetic, from a history k_hist_exact repairs first -- launch_shape's auto_ok, the tail
-    // being too short to leave the mixed samples behind) -- true when the call should be cut that way.
-    if (!(g.arith == SELENITE_ARITH_SPLIT16 || g.arith == SELENITE_ARITH_AUTO) || !plan.d_btab16 || !g.nd_taps) return false;
-    const uint32_t pq = split16_pass_out(g.block, g.decim), unit = pq * g.decim;
-    if (!split16_pass_ok(pq) || block_size % unit == 0 || block_size < unit) return false;
-    const int nds = split16_template_nd((int)g.nd_taps, (int)g.decim, (int)g.nh_taps);
-    if (nds < 0) return false;
-    const uint32_t hq = ((uint32_t)nds - 1 + g.decim - 1) / g.decim, hs = ((hq + 3) & ~3u) * g.decim;    // GeoS::HS
-    return block_size % unit < hs;
-}
-
-hipError_t launch_fused(const FusedPlan &plan, const RxParams &p, int arith, const void *src, bool src_q15,
+hipError_t launch_fused(const FusedPlan &plan, const RxParams &p, const Decision &d, const void *src, bool src_q15,
                         void *dst, bool dst_q15, int delay_index, hipStream_t st)
 {
+    if (src_q15 != d.q15 || dst_q15 != d.q15) return hipErrorNotSupported;      // (the fused kernels convert in and out symmetrically)
     FusedArgs fa;
     fa.cq = plan.d_cq;
     fa.delay_idx = (uint32_t)delay_index;
     fa.upper = mode_is_upper(p.mode) ? 1u : 0u;
     fa.am = p.mode == SELENITE_MODE_AM ? 1u : (p.mode == SELENITE_MODE_FM ? 2u : 0u);      // (FM: a run-time flavour of the AM instantiations of k_ssb_fused)
     fa.group = (p.block / p.decim) / 4;
-    fa.pass_out = 256u / (p.block / p.decim) * (p.block / p.decim);
+    fa.pass_out = d.pass_out;
+    fa.nco = d.nco;
     fa.btab16 = plan.d_btab16;
     fa.split_post = plan.split_post;
     fa.split_sc = plan.split_sc;
-    fa.inl = 0u;                                          // (launch_shape: SELENITE_ARITH_AUTO in one launch)
-    fa.dec2 = 0u;                                         // (launch_shape sets it for decimation by 8 on the by-4 matrix kernel)
+    fa.inl = d.auto_form == 1u ? 1u : 0u;                 // SELENITE_ARITH_AUTO in one launch
+    fa.dec2 = 0u;
+    if (d.dec2) {
+        // decimation by 8 on the by-4 matrix kernel.  Which half: the tile's output j ends at input sample 4 j of the pass in this kernel's
+        // bookkeeping, a by-8 output n at 8 n -- the even ones; SELENITE_RX_DEC2_PARITY=2 selects the odd ones: a diagnostic that shows
+        // the tests notice (only the value 2 is taken, and said so on stderr: anything else keeps the chain's outputs)
+        static const uint32_t par = [] {
+            const char *e = diag_env("SELENITE_RX_DEC2_PARITY");
+            if (e && e[0] == '2' && e[1] == 0) { fprintf(stderr, "selenite_rx: SELENITE_RX_DEC2_PARITY=2 -- decimation by 8 keeps the ODD by-4 outputs (diagnostic, wrong audio)\n"); return 2u; }
+            return 1u;
+        }();
+        fa.dec2 = par;
+    }
     {
         static const uint32_t shift = [] {                // (diagnostic builds: another workgroup -> channel-group mapping; read once, 0 .. 8)
             const char *e = diag_env("SELENITE_RX_GRP_SHIFT");
@@ -776,16 +570,15 @@ hipError_t launch_fused(const FusedPlan &plan, const RxParams &p, int arith, con
         }();
         fa.grp_shift = shift;
     }
-    if (plan.dense) {
-        // the FIR pair with arbitrary taps: k_ssb_fused's DENSE flavour, bit-exact (CMSIS; AUTO runs as CMSIS) or fma (FMA; SPLIT16 runs as fma)
-        if (src_q15 != dst_q15) return hipErrorNotSupported;
+    if (plan.sel.dense) {
+        // the FIR pair with arbitrary taps: k_ssb_fused's DENSE flavour, bit-exact or fma
         fa.ptab = plan.d_ptab;
         fa.ptab_lds = nullptr;
         fa.dense_t0 = plan.dense_t0;
         if (plan.dense_delay_impulse) fa.delay_idx = (uint32_t)delay_index + (127u - p.nh);      // the unit tap's index among the padded taps
-        const bool exact = arith == SELENITE_ARITH_CMSIS || arith == SELENITE_ARITH_AUTO;
+        const bool exact = d.family == kDenseExact;
 #define X(ND_, M_, NH_, ID_)                                                                                          \
-        if (plan.kind == ID_) {                                                                                       \
+        if (plan.sel.kind == ID_) {                                                                                     \
             if (exact) return launch_exact_dense(ND_, M_, src_q15, plan.dense_delay_impulse, p, fa, src, dst, st);    \
             if (plan.dense_delay_impulse)                                                                             \
                 return src_q15 ? launch_one<1, ND_, M_, NH_, int16_t, int16_t, 2>(p, fa, src, dst, st)                \
@@ -798,7 +591,7 @@ hipError_t launch_fused(const FusedPlan &plan, const RxParams &p, int arith, con
         return hipErrorNotSupported;
     }
 #define X(ND_, M_, NH_, ID_) \
-    if (plan.kind == ID_) return launch_shape<ND_, M_, NH_>(p, fa, plan, arith, src, src_q15, dst, dst_q15, st);
+    if (plan.sel.kind == ID_) return launch_shape<ND_, M_, NH_>(p, fa, plan, d, src, src_q15, dst, st);
     SRX_SHAPES(X)
 #undef X
     return hipErrorNotSupported;

@@ -41,8 +41,8 @@ struct FusedArgs {
     uint32_t upper;         // 1: audio = I' - Q'   0: audio = I' + Q'
     uint32_t am;            // 1: audio = |I + jQ| (arm_cmplx_mag_f32); the Hilbert pair and its state are untouched
                             // 2: FM -- angle of z[n] conj(z[n-1]) in half turns; the pair's delay lines keep running (k_ssb_fused only)
-    uint32_t nco;           // k_ssb_fused: NCO flavour of the launch (0 off, 1 per channel per sample, 2 shared table, 4 per-channel periodic LO
-                            // in registers) -- a run-time switch since round 4 (launch_one sets it)
+    uint32_t nco;           // NCO flavour of the launch (Decision::nco: 0 off, 1 per channel per sample, 2 shared table, 3 / 4 shared / per-channel
+                            // periodic LO in registers) -- a run-time switch of k_ssb_fused since round 4, the launchers' template choice elsewhere
     const float *ptab;      // DENSE instantiations of k_ssb_fused: the FIR pair's taps, [2][DenseTab::LEN] (delay rail, Hilbert rail), padded tap k at index k + FH + 3
     float *ptab_lds;        // ... their copy in LDS (set by the kernel)
     uint32_t dense_t0;      // ... first step with a tap that is not padding
@@ -59,6 +59,19 @@ struct FusedArgs {
                             // pass_out * 2 M input samples and only every second output of the tile is an output of the chain (1: the even ones,
                             // 2: the odd ones); 0: the plain by-M kernel
 };
+
+// Persistent grids: workgroups of kernel k the device keeps resident, or -1 (unknown, or `env` says 0: one workgroup per channel); `env` overrides
+template <typename K>
+static int resident_workgroups(K k, int threads, size_t lds, const char *env)
+{
+    int per_cu = 0, dev = 0, n = -1;
+    hipDeviceProp_t prop;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, threads, lds) == hipSuccess && per_cu > 0 && hipGetDevice(&dev) == hipSuccess &&
+        hipGetDeviceProperties(&prop, dev) == hipSuccess)
+        n = per_cu * prop.multiProcessorCount;
+    if (const char *e = diag_env(env)) n = std::atoi(e) > 0 ? std::atoi(e) : -1;
+    return n;
+}
 
 // Workgroups of these kernels are ONE wavefront: LDS instructions of a wave execute in issue order,
 // so a store is visible to any lane's later load without s_barrier.  What is needed is only that
@@ -346,10 +359,7 @@ struct GeoH {
     static_assert(HH % 2 == 0 && HH <= 256, "Hilbert history");
 };
 
-// instantiated shapes of the two kernel families (ND, M, NH) / (NH)
-#define SRX_SPLIT16_SHAPES(X) X(256, 4, 63) X(128, 4, 63) X(256, 4, 127) X(128, 4, 127) X(256, 4, 31) X(128, 4, 31) \
-                              X(256, 2, 63) X(128, 2, 63) X(256, 2, 127) X(128, 2, 127) X(256, 2, 31) X(128, 2, 31)
-#define SRX_HILB16_SHAPES(X) X(63) X(127) X(31)
+// (the instantiated shapes of the two kernel families, SRX_SPLIT16_SHAPES and SRX_HILB16_SHAPES: rx_select.h)
 hipError_t launch_ssb_split16(int nd, int m, int nh, const RxParams &p, const FusedArgs &fa, const void *src, bool q15,
                               void *dst, hipStream_t st);
 hipError_t launch_hilb_split16(int nh, const RxParams &p, const FusedArgs &fa, const void *src, bool q15, void *dst,

@@ -14,7 +14,6 @@
 
 namespace srx {
 
-
 // arm_fir_decimate_f32 on BOTH rails for the 4 adjacent outputs j = 4*lane + r.
 // Output j needs s[(j - HQ4 + q)*M + p] * cq[q*M + p], q = 0..HQ4 ascending, p ascending: the
 // loops below visit (q, p) in exactly that order for every r, so each accumulator sees the
@@ -647,16 +646,12 @@ __global__ __launch_bounds__(64, 2) void k_ssb_fused(RxParams p, FusedArgs fa, c
     ssb_fused_body<ARITH, ND, M, NH, TIn, TOut, DENSE, false>(p, fa, src, dst, FusedInl{ 0u, 0u });
 }
 
-
 template <int ARITH, int ND, int M, int NH, typename TIn, typename TOut, int DENSE = 0>
-static hipError_t launch_one(const RxParams &p, const FusedArgs &fa_in, const void *src, void *dst, hipStream_t st)
+static hipError_t launch_one(const RxParams &p, const FusedArgs &fa, const void *src, void *dst, hipStream_t st)
 {
     using G = Geo<ND, M, NH>;
     constexpr size_t lds = ((size_t)G::total + (DENSE ? 2 * DenseTab<NH>::LEN : 0)) * sizeof(float);
-    FusedArgs fa = fa_in;
-    // NCO flavour of the launch: shared table (2); per-channel LO with a period of 256 samples (every step a multiple of 2^24) and
-    // 256-output passes: one period per channel in registers (4); per channel per sample (1); off (0)
-    fa.nco = p.nco == 2 ? 2u : (p.nco == 1 ? ((p.lo_period == 256 && fa.pass_out == 256) ? 4u : 1u) : 0u);
+    if (fa.nco == 3u || (fa.nco == 4u && fa.pass_out != 256u)) return hipErrorNotSupported;      // (rx_select.h: fused_nco)
     auto k = k_ssb_fused<ARITH, ND, M, NH, TIn, TOut, DENSE>;
     if constexpr (lds > 48 * 1024) {                      // per device and per kernel: set on every launch (cheap)
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k),
@@ -680,14 +675,7 @@ static hipError_t launch_one(const RxParams &p, const FusedArgs &fa_in, const vo
     return hipGetLastError();
 }
 
-// the instantiated shapes: BASELINE.json cfg1 / cfg2 / cfg3 (+ cfg5 = cfg2 chain) and their neighbours in both
-// tap counts -- decimator 128 / 256 taps by 4, Hilbert pair 31 / 63 / 127 taps, with or without the decimator
-#define SRX_SHAPES(X) X(256, 4, 63, 1) X(0, 1, 63, 2) X(0, 1, 127, 3) X(128, 4, 63, 4) X(256, 4, 127, 5) X(128, 4, 127, 6) X(256, 4, 31, 7) X(0, 1, 31, 8) \
-                      X(256, 2, 63, 9) X(256, 8, 63, 10) X(64, 4, 63, 11) X(128, 2, 63, 12) X(128, 8, 63, 13) X(64, 2, 63, 14) X(64, 8, 63, 15) \
-                      X(128, 4, 31, 16) X(256, 2, 127, 17) X(128, 2, 127, 18) X(256, 2, 31, 19) X(128, 2, 31, 20)
-
-// ... and the shapes of the DENSE flavour (any FIR pair of up to 127 taps with arbitrary taps on both rails; any decimator up to the shape's)
-#define SRX_DENSE_SHAPES(X) X(256, 4, 127, 101) X(128, 4, 127, 102) X(256, 2, 127, 103) X(128, 2, 127, 104) X(256, 8, 127, 105) X(128, 8, 127, 106) X(0, 1, 127, 107)
+// (the instantiated shapes, SRX_SHAPES and SRX_DENSE_SHAPES: rx_select.h)
 hipError_t launch_exact_dense(int nd, int m, bool q15, bool delay_impulse, const RxParams &p, const FusedArgs &fa, const void *src, void *dst, hipStream_t st);
 
 // the CMSIS-arithmetic instantiations live in rx_fused_exact.hip

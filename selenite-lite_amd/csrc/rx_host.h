@@ -72,6 +72,8 @@ enum Phase { kAll, kPhase1, kPhase2 };
 struct CallStart { uint32_t phase; uint64_t spec_pos; };
 inline CallStart call_start(const selenite_rx_instance *S) { return CallStart{ S->phase_host, S->spec.pos }; }
 inline ChanRange all_channels(const selenite_rx_instance *S) { return ChanRange{ 0u, S->cfg.channels }; }
+// this instance's calls run on the SSB fused kernels (rx_fused.hip), as select() (rx_select.h) decides call by call
+inline bool on_ssb_fused(const selenite_rx_instance *S) { return !S->force_generic && S->plan.sel.kind != 0; }
 
 bool block_size_ok(selenite_rx_instance *S, uint32_t block_size, const char *who);
 RxParams make_params(selenite_rx_instance *S, ChanRange r, uint32_t block_size);

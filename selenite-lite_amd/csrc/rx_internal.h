@@ -9,6 +9,7 @@
 #include "../../include/selenite_rx.h"
 #include "rx_device.h"
 #include "rx_diag.h"
+#include "rx_select.h"
 
 struct selenite_rx_instance;
 
@@ -27,7 +28,7 @@ struct RxParams {
     uint32_t nh;           // Hilbert / delay taps (0 = none)
     uint32_t nbiq;         // biquad stages
     uint32_t mode;         // SELENITE_MODE_*
-    uint32_t nco;          // 0 = off, 1 = per-channel LO computed in the kernel, 2 = shared LO table `lo`
+    uint32_t nco;          // 0 = off, 1 = per-channel LO computed in the kernel, 2 = shared LO table `lo` (Decision::nco_rx)
     uint32_t agc;          // AGC enabled
     uint32_t block_size;   // input samples per channel in this call
     uint32_t nout;         // block_size / decim
@@ -258,7 +259,7 @@ struct __attribute__((visibility("hidden"))) NbStage {
 
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
-    int kind = 0;                 // 0 = none
+    SelPlan sel;                  // what select() reads: the shape (kind 0 = none), dense or not, which operands exist (rx_select.h)
     const char *name = "generic";
     std::string name_buf;         // storage behind `name` for the composed kernel names
     float *d_cq = nullptr;        // zero-padded decimator taps in the fused kernel's indexing
@@ -266,36 +267,16 @@ struct FusedPlan {
     void *d_btab16 = nullptr;     // same operand split into f16 hi / lo parts (SELENITE_ARITH_SPLIT16)
     float split_post = 1.0f;      // 2^-(sample scale + tap scale) applied to the split-precision result (k_hilb_split16)
     int split_sc = 0;             // tap scale exponent of the split-precision decimator (k_ssb_split16)
-    bool use_mfma = false;        // FMA arithmetic: decimator on the matrix cores
-    bool dense = false;           // the DENSE flavour of k_ssb_fused: a FIR pair with arbitrary taps (kind = an ID of SRX_DENSE_SHAPES)
-    float *d_ptab = nullptr;      // ... its tap tables [2][DenseTab::LEN]
+    float *d_ptab = nullptr;      // the DENSE flavour of k_ssb_fused: its tap tables [2][DenseTab::LEN]
     uint32_t dense_t0 = 0;        // ... first FIR step with a tap that is not padding
     bool dense_delay_impulse = false;   // ... the delay FIR is a unit impulse (only the Hilbert FIR runs dense)
     bool tables_built = false;
 };
-hipError_t plan_fused(const selenite_rx_config &cfg, bool delay_is_impulse, int delay_index,
-                      bool hilb_odd_only, FusedPlan &plan);
+hipError_t plan_fused(const selenite_rx_config &cfg, bool delay_is_impulse, bool hilb_odd_only, FusedPlan &plan);
 void free_fused(FusedPlan &plan);
-// passes k_ssb_split16 runs: 256 audio samples, or fewer when the DSP block does not divide 256 -- whole 16-output tiles
-inline bool split16_pass_ok(uint32_t pass_out) { return pass_out != 0 && pass_out <= 256u && pass_out % 16u == 0; }
-// audio samples a full pass of k_ssb_split16 produces: the largest whole number of DSP blocks in its tile -- 256 outputs, or 128 when the
-// chain decimates by 8 (the by-4 product with every second output kept: FusedArgs::dec2)
-inline uint32_t split16_pass_out(uint32_t block, uint32_t decim)
-{
-    const uint32_t na = decim ? block / decim : 0u;
-    return na ? (decim == 8u ? 128u : 256u) / na * na : 0u;
-}
-bool fused_tail_split(const FusedPlan &plan, const selenite_rx_config &cfg, uint32_t block_size);
-hipError_t launch_fused(const FusedPlan &plan, const RxParams &p, int arith, const void *src,
+// launches what `d` names (rx_select.h: select) -- the kernel, and the launches SELENITE_ARITH_AUTO puts in front of and behind it
+hipError_t launch_fused(const FusedPlan &plan, const RxParams &p, const Decision &d, const void *src,
                         bool src_q15, void *dst, bool dst_q15, int delay_index, hipStream_t st);
-
-// the instantiated decimator length that serves an instance of nd taps (its taps zero-padded in front): fused kernels / k_ssb_split16; -1: none
-int fused_template_nd(int nd, int m, int nh);
-int split16_template_nd(int nd, int m, int nh);
-// true when k_ssb_split16 of this shape has the periodic-LO flavour (a pass is a whole number of 256-sample periods)
-bool ssb_split16_periodic_lo(int nd, int m, int nh);
-// true when rx_split16.hip instantiates k_ssb_split16 for this shape
-bool ssb_split16_has_shape(int nd, int m, int nh);
 
 // fused CW kernel (rx_cw.hip): NCO -> real part -> 4-stage biquad cascade -> AGC
 bool cw_fused_ok(const selenite_rx_config &cfg, uint32_t block_size);

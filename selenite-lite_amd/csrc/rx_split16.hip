@@ -28,22 +28,10 @@
 
 namespace srx {
 
-bool ssb_split16_has_shape(int nd, int m, int nh)
-{
-#define X(ND_, M_, NH_) if (nd == ND_ && m == M_ && nh == NH_) return true;
-    SRX_SPLIT16_SHAPES(X)
+// rx_select.h does its arithmetic without the kernels' geometry: its history length is this kernel's, and a full pass is whole LO periods
+#define X(ND_, M_, NH_) static_assert(split16_hs(ND_, M_) == GeoS<2, ND_, M_, NH_>::HS && Geo<ND_, M_, NH_>::T % 256 == 0, "rx_select.h: split16_hs / pass_is_lo_periods");
+SRX_SPLIT16_SHAPES(X)
 #undef X
-    return false;
-}
-
-bool ssb_split16_periodic_lo(int nd, int m, int nh)
-{
-    if (m == 8) m = 4;                                    // (decimation by 8 runs the by-4 kernel: FusedArgs::dec2)
-#define X(ND_, M_, NH_) if (nd == ND_ && m == M_ && nh == NH_) return Geo<ND_, M_, NH_>::T % 256 == 0;
-    SRX_SPLIT16_SHAPES(X)
-#undef X
-    return false;
-}
 
 hipError_t launch_ssb_split16(int nd, int m, int nh, const RxParams &p, const FusedArgs &fa, const void *src, bool q15,
                               void *dst, hipStream_t st)
@@ -61,10 +49,11 @@ static hipError_t launch_hilb16(const RxParams &p, const FusedArgs &fa, const vo
     using GH = GeoH<NH>;
     constexpr size_t lds = (size_t)(Geo<0, 1, NH>::total > GH::total ? Geo<0, 1, NH>::total : GH::total) * sizeof(float);     // (+ the bit-exact kernel's image: FusedArgs::inl)
     static_assert(lds <= 48 * 1024, "k_hilb_split16 LDS image");
-    auto k = fa.am ? (p.nco == 2 ? k_hilb_split16<2, NH, TIn, TOut, 1>
-                                 : (p.nco == 1 ? k_hilb_split16<1, NH, TIn, TOut, 1> : k_hilb_split16<0, NH, TIn, TOut, 1>))
-                   : (p.nco == 2 ? k_hilb_split16<2, NH, TIn, TOut, 0>
-                                 : (p.nco == 1 ? k_hilb_split16<1, NH, TIn, TOut, 0> : k_hilb_split16<0, NH, TIn, TOut, 0>));
+    if (fa.nco > 2u) return hipErrorNotSupported;                  // (no register-held LO flavour)
+    auto k = fa.am ? (fa.nco == 2 ? k_hilb_split16<2, NH, TIn, TOut, 1>
+                                  : (fa.nco == 1 ? k_hilb_split16<1, NH, TIn, TOut, 1> : k_hilb_split16<0, NH, TIn, TOut, 1>))
+                   : (fa.nco == 2 ? k_hilb_split16<2, NH, TIn, TOut, 0>
+                                  : (fa.nco == 1 ? k_hilb_split16<1, NH, TIn, TOut, 0> : k_hilb_split16<0, NH, TIn, TOut, 0>));
     hipLaunchKernelGGL(k, dim3(p.channels), dim3(64), lds, st, p, fa, static_cast<const TIn *>(src),
                        static_cast<TOut *>(dst));
     return hipGetLastError();

@@ -1109,7 +1109,7 @@ __global__ __launch_bounds__(64, 2) void k_hilb_split16(RxParams p, FusedArgs fa
     } while (0);
     if constexpr (INLT) {
         if (word_t != 0u) {                                           // wave-uniform
-            RxParams p2 = p;                                          // the rerun pass's view (rx_fused.hip: launch_shape, rerun())
+            RxParams p2 = p;                                          // the rerun pass's view (rx_fused.hip: launch_shape, behind the matrix kernel)
             p2.chan_flags = p.rerun_flag;
             p2.rerun_flag = nullptr;
             p2.chan_list = nullptr; p2.chan_count = nullptr; p2.chan_count_next = nullptr; p2.rerun_seen = nullptr;
@@ -1133,17 +1133,7 @@ static hipError_t launch_k(const RxParams &p, const FusedArgs &fa, const void *s
     if (fa.inl) return hipErrorNotSupported;                      // (the one-launch form of SELENITE_ARITH_AUTO: k_hilb_split16 only)
     // persistent grid: as many single-wave workgroups as the device keeps resident, each running channels
     // b, b + grid, b + 2 grid, ...  (SELENITE_RX_SPLIT16_GRID=0: one workgroup per channel, the round-1 launch shape)
-    static int resident = 0;
-    if (resident == 0) {
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ssb_split16<NCO, ND, M, NH, TIn, TOut, AM, GROUP, FLAVOUR>, 64, lds) != hipSuccess ||
-            hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || per_cu <= 0)
-            resident = -1;
-        else
-            resident = per_cu * prop.multiProcessorCount;
-        if (const char *e = diag_env("SELENITE_RX_SPLIT16_GRID")) resident = std::atoi(e) > 0 ? std::atoi(e) : -1;
-    }
+    static const int resident = resident_workgroups(k_ssb_split16<NCO, ND, M, NH, TIn, TOut, AM, GROUP, FLAVOUR>, 64, lds, "SELENITE_RX_SPLIT16_GRID");
     const uint32_t grid = resident > 0 && (uint32_t)resident < p.channels ? (uint32_t)resident : p.channels;
     if constexpr (GROUP == 16 && AM == 0 && sizeof(TOut) == 4) {
         if (p.env_part) {                         // global gain, phase 1: the flavour that also leaves the block maxima behind
@@ -1184,12 +1174,13 @@ template <int ND, int M, int NH, typename T>
 static hipError_t launch_nco(const RxParams &p, const FusedArgs &fa, const void *src, void *dst, hipStream_t st)
 {
     if constexpr (Geo<ND, M, NH>::T % 256 == 0) {
-        if (p.nco == 2 && p.lo_period == 256) return launch_io<3, ND, M, NH, T, T>(p, fa, src, dst, st);      // LO held in registers
-        if (p.nco == 1 && p.lo_period == 256) return launch_io<4, ND, M, NH, T, T>(p, fa, src, dst, st);      // every channel its own LO on the fs / 256 grid: in registers, computed once per channel
+        if (fa.nco == 3) return launch_io<3, ND, M, NH, T, T>(p, fa, src, dst, st);      // LO held in registers
+        if (fa.nco == 4) return launch_io<4, ND, M, NH, T, T>(p, fa, src, dst, st);      // every channel its own LO on the fs / 256 grid: in registers, computed once per channel
     }
-    if (p.nco == 2) return launch_io<2, ND, M, NH, T, T>(p, fa, src, dst, st);
-    if (p.nco == 1) return launch_io<1, ND, M, NH, T, T>(p, fa, src, dst, st);
-    return launch_io<0, ND, M, NH, T, T>(p, fa, src, dst, st);
+    if (fa.nco == 2) return launch_io<2, ND, M, NH, T, T>(p, fa, src, dst, st);
+    if (fa.nco == 1) return launch_io<1, ND, M, NH, T, T>(p, fa, src, dst, st);
+    if (fa.nco == 0) return launch_io<0, ND, M, NH, T, T>(p, fa, src, dst, st);
+    return hipErrorNotSupported;
 }
 
 // the int16-slot instantiations of k_ssb_split16 live in rx_split16_q15.hip (a translation unit of its own: compiles in parallel)

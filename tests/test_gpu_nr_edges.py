@@ -221,7 +221,7 @@ def own_audio(mk, calls, kind, n, d, mu, q15=False):
 
 @pytest.mark.parametrize("arith", [rc.ARITH_SPLIT16, rc.ARITH_AUTO], ids=["split16", "auto"])
 @pytest.mark.parametrize("q15", [False, True], ids=["f32", "q15"])
-@pytest.mark.parametrize("name,ch,calls", [("cfg3", 70, [1280, 4096 + 256]),             # whole passes + a tail cut off for k_ssb_fused (fused_tail_split)
+@pytest.mark.parametrize("name,ch,calls", [("cfg3", 70, [1280, 4096 + 256]),             # whole passes + a tail cut off as a call of its own (rx_select.h)
                                            ("cfg3_by8", 64, [1024 + 256, 4096 + 256, 256]),
                                            ("cfg2_48k128", 130, [128 * 5, 128, 128 * 8]),
                                            ("cfg2_48k", 96, [192 * 5, 192, 192 * 4])])

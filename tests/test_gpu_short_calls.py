@@ -146,8 +146,10 @@ def test_am_and_global_gain_with_partial_passes():
 @pytest.mark.parametrize("arith", [rc.ARITH_SPLIT16, ARITH_AUTO])
 def test_a_tail_too_short_for_the_matrix_kernel_is_cut_off_and_runs_on_the_variable_length_kernel(arith):
     """DSP block 128 behind the 256-tap /4 decimator: a call of 1024 k + 128 samples ends in a partial pass that holds less than
-    a decimator history -- the whole passes stay on k_ssb_split16, the tail goes to k_ssb_fused (fused_tail_split), same
-    streaming state.  Raw split16: input-referred bar; AUTO: plain bar."""
+    a decimator history -- the call is cut (rx_select.h: Decision::first): the whole passes are one launch of k_ssb_split16, the tail a
+    call of its own on the same streaming state.  The tail is shorter than a pass, which k_ssb_split16 takes: raw split16 runs it there
+    (the kernel trace of profiles/select shows two k_ssb_split16 launches per such call); AUTO runs it on the bit-exact k_ssb_fused, the
+    tail being too short to leave the repair rows behind.  Raw split16: input-referred bar; AUTO: plain bar."""
     import selenite_rx as sr
     nch, na = 33, 32
     kw = dict(nco=True, nco_step_all=0x01000000, agc=arith == ARITH_AUTO)

@@ -4,7 +4,10 @@ of shapes, arithmetics and slot formats on seeded input: run it with two builds 
 not meant to change a bit did not (`SELENITE_RX_LIB=old.so python3 tools/output_hashes.py > a; python3 tools/output_hashes.py > b; diff a b`).
 The stage rows behind them (NLMS, output stage, spectrum tap: each alone and all three, f32 and int16 slots, device calls and host-pointer
 calls cut into 1 MiB channel chunks) hash the audio, the chain state and the stages' state; they run in a child process, because the library
-reads SELENITE_RX_HOST_CHUNK_MB once."""
+reads SELENITE_RX_HOST_CHUNK_MB once (`--stage-rows` alone: only those, in this process).  Between the two, the edge rows: calls at the
+edges of the rule that picks the kernel of a call (csrc/rx_select.h) -- short calls, partial passes, cut calls, the AUTO forms, FM, the
+dense flavour, the five LO situations, global gain, NLMS, the repair switched off, the generic path -- 33 channels, three calls each, with
+the kernel name, the NCO path and the form of the last AUTO launch beside the hash (`--chain-rows`: these and the chain rows, no child)."""
 import hashlib
 import os
 import subprocess
@@ -92,12 +95,103 @@ def chain_rows():
                     rx.close()
 
 
+N_EDGE = 33
+GRID, OFFGRID = 0x01000000, 0x01234567            # NCO steps on and off the fs / 256 grid
+
+
+def edge_row(label, spec, bs, q15=False, setup=None):
+    rx = sr.Rx(spec.config())
+    if setup:
+        setup(rx)
+    h = hashlib.sha256()
+    for call in range(3):
+        iq = sr.synth_iq_host(0, N_EDGE, call * bs, bs, ch.SEED)
+        try:
+            if q15:
+                y = rx.process_q15(np.clip(np.trunc(iq * 32768.0), -32768, 32767).astype(np.int16))
+            else:
+                y = rx.process(iq)
+        except sr.RxError as e:                   # (a refused call is a row too: both builds must refuse it alike)
+            print("edge", label, bs, "q15" if q15 else "f32", "|", rx.kernel_name(), "| refused:", e)
+            rx.close()
+            return
+        h.update(np.ascontiguousarray(y).tobytes())
+    st = rx.state()
+    for k in sorted(st):
+        h.update(np.ascontiguousarray(st[k]).tobytes())
+    print("edge", label, bs, "q15" if q15 else "f32", "|", rx.kernel_name(), "|", rx.nco_path(), "|", rx.auto_launches_last(), h.hexdigest()[:24])
+    rx.close()
+
+
+def edge_rows():
+    n = N_EDGE
+    own_steps = (np.arange(n, dtype=np.uint64) * 0x9E3779B1 % (1 << 32)).astype(np.uint32)      # most channels rerun exactly under AUTO
+    grid_steps = ((np.arange(n, dtype=np.uint32) % 7 + 1) << 24).astype(np.uint32)
+    los = [("lo-off", dict(nco=False)), ("lo-shared", dict(nco=True, nco_step_all=OFFGRID)), ("lo-shared-grid", dict(nco=True, nco_step_all=GRID)),
+           ("lo-own-grid", dict(nco=True, nco_steps=grid_steps)), ("lo-own", dict(nco=True, nco_steps=own_steps))]
+
+    def cfg3(arith, block=256, decim=4, nh=63, mode=sr.MODE_USB, **kw):
+        kw.setdefault("nco", True)
+        if "nco_steps" not in kw:
+            kw.setdefault("nco_step_all", GRID)
+        return ch.ChainSpec(n, block, decim, 256, nh, 0, mode, arith, **kw)
+
+    def cfg2(arith, block=256, mode=sr.MODE_USB, **kw):
+        return ch.ChainSpec(n, block, 1, 0, 127, 0, mode, arith, **kw)
+
+    def launches(k):
+        return lambda rx: rx.set_auto_launches(k)
+
+    autos = [("split16", sr.ARITH_SPLIT16, {}, None), ("auto-1", sr.ARITH_AUTO, dict(nco_steps=own_steps), launches(1)),
+             ("auto-3", sr.ARITH_AUTO, dict(nco_steps=own_steps), launches(3))]
+    for tag, arith, kw, setup in autos:
+        for bs in (128, 256, 512, 1152, 1408, 2176):              # under a pass, a pass and a tail under / over the decimator history
+            edge_row("cfg3-b128 " + tag, cfg3(arith, 128, **kw), bs, setup=setup)
+        for bs in (96, 960, 1056):                                # the firmware geometry: passes of 240 outputs
+            edge_row("cfg3-b96 " + tag, cfg3(arith, 96, **kw), bs, setup=setup)
+        for bs in (1024, 1280):                                   # by 8: one pass of 128 outputs, and a block more
+            edge_row("cfg3-by8 " + tag, cfg3(arith, 256, 8, **kw), bs, setup=setup)
+    for block in (128, 192):
+        for bs in (block, 256 // block * block, 256 // block * block + block):
+            edge_row("cfg2-b%d auto-1" % block, cfg2(sr.ARITH_AUTO, block), bs, setup=launches(1))
+            edge_row("cfg2-b%d auto-3" % block, cfg2(sr.ARITH_AUTO, block), bs, setup=launches(3))
+            edge_row("cfg2-b%d auto-1 am" % block, cfg2(sr.ARITH_AUTO, block, sr.MODE_AM), bs, setup=launches(1))
+    for tag, arith in (("fma", sr.ARITH_FMA), ("split16", sr.ARITH_SPLIT16), ("auto", sr.ARITH_AUTO)):
+        edge_row("cfg3 fm " + tag, cfg3(arith, mode=sr.MODE_FM), 1024)
+        edge_row("cfg2 fm " + tag, cfg2(arith, mode=sr.MODE_FM), 1024)
+    for bs in (2048, 1280):
+        edge_row("cfg3 fma", cfg3(sr.ARITH_FMA), bs)
+    for tag, arith in (("cmsis", sr.ARITH_CMSIS), ("fma", sr.ARITH_FMA), ("auto", sr.ARITH_AUTO)):      # the dense flavour
+        edge_row("cfg3 65-tap pair " + tag, cfg3(arith, nh=65), 1024)
+        spec = cfg3(arith)
+        spec.delay = ch.design_lowpass(63, 0.2)
+        edge_row("cfg3 delay FIR " + tag, spec, 1024)
+    for block, bs in ((256, 2048), (96, 960)):
+        for tag, arith in (("cmsis", sr.ARITH_CMSIS), ("fma", sr.ARITH_FMA), ("split16", sr.ARITH_SPLIT16), ("auto", sr.ARITH_AUTO)):
+            for lo, kw in los:
+                edge_row("cfg3-b%d %s %s" % (block, lo, tag), ch.ChainSpec(n, block, 4, 256, 63, 0, sr.MODE_USB, arith, **kw), bs)
+    for tag, arith in (("split16", sr.ARITH_SPLIT16), ("auto", sr.ARITH_AUTO)):
+        edge_row("cfg3 global " + tag, cfg3(arith, agc_global=True), 2048)
+        edge_row("cfg3 global " + tag, cfg3(arith, agc_global=True), 768)
+        edge_row("cfg3 global " + tag, cfg3(arith, agc_global=True), 2048, q15=True)
+    for q15 in (False, True):
+        edge_row("cfg3 nlms auto", cfg3(sr.ARITH_AUTO, nco_steps=own_steps), 2048, q15, lambda rx: rx.set_nr(sr.NR_DENOISE, num_taps=16, delay=8, mu=0.05))
+    for bs in (256, 1152):
+        edge_row("cfg3-b128 no-repair auto", cfg3(sr.ARITH_AUTO, 128, nco_steps=own_steps), bs, setup=lambda rx: rx.set_handover_repair(0))
+    with sr.plan_option(sr.OPT_FORCE_GENERIC):
+        edge_row("cfg3 force-generic auto", cfg3(sr.ARITH_AUTO, nco_steps=own_steps), 1024)
+        edge_row("cfg2 force-generic auto", cfg2(sr.ARITH_AUTO), 1024)
+
+
 def main():
     if sys.argv[1:] == ["--stage-rows"]:
         stage_rows()
         return 0
     chain_rows()
+    edge_rows()
     sys.stdout.flush()
+    if sys.argv[1:] == ["--chain-rows"]:
+        return 0
     # a fresh child process: the library reads SELENITE_RX_HOST_CHUNK_MB once
     return subprocess.run([sys.executable, os.path.abspath(__file__), "--stage-rows"], env=dict(os.environ, SELENITE_RX_HOST_CHUNK_MB="1")).returncode
 
