@@ -13,13 +13,31 @@ namespace srx {
 // streaming state of a channel: written by one call and read back by the next -- 0.17 GB for 65 536 channels, which the 256 MB
 // Infinity Cache can hold between calls if nothing streams through it: plain (cacheable) accesses (non-temporal ones measured
 // 1.6 % slower: they defeat exactly that residency)
-__device__ __forceinline__ float st_ld(const float *p)
+// k_ssb_split16 reaches it through buffer descriptors (make_rsrc): a scalar base per channel and a 32-bit lane offset instead of a
+// 64-bit address per lane and access, the range check instead of an exec mask -- with the same, default cache policy (aux 0)
+__device__ __forceinline__ uint32_t st_ld(__amdgpu_buffer_rsrc_t r, int voff, int soff)
 {
-    return *p;
+    return __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0);
 }
-__device__ __forceinline__ void st_st(float *p, float v)
+__device__ __forceinline__ void st_st(__amdgpu_buffer_rsrc_t r, int voff, int soff, uint32_t v)
 {
-    *p = v;
+    __builtin_amdgcn_raw_buffer_store_b32(v, r, voff, soff, 0);
+}
+__device__ __forceinline__ v2f st_ld2(__amdgpu_buffer_rsrc_t r, int voff, int soff)      // 8 bytes: rows and offsets that are even words only
+{
+    const u2v w = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
+    return v2f{ __uint_as_float(w.x), __uint_as_float(w.y) };
+}
+__device__ __forceinline__ void st_st2(__amdgpu_buffer_rsrc_t r, int voff, int soff, v2f v)
+{
+    __builtin_amdgcn_raw_buffer_store_b64(u2v{ __float_as_uint(v.x), __float_as_uint(v.y) }, r, voff, soff, 0);
+}
+// lane offset of an access that must not happen: beyond every range of this file (loads return zeros, stores are dropped)
+constexpr int kStOob = 0x40000000;
+// byte offset `b` of a lane into a state row, or kStOob when the lane sits in front of the row (b < 0)
+__device__ __forceinline__ int st_off(int b)
+{
+    return (int)min((uint32_t)b, (uint32_t)kStOob);
 }
 
 // sticky per-channel counters do not wrap (advisor, round 3: a uint32 of guarded blocks wraps after days at firmware slot rates)
@@ -343,34 +361,40 @@ __global__ __launch_bounds__(64, 2) void k_ssb_split16(RxParams p, FusedArgs fa,
     // ---- streaming state of a channel: loaded into registers (for the next channel of this workgroup while
     // the current one is still in its last pass), installed into LDS when the channel starts.  Flat history
     // sample f in [0, HS) is CMSIS state sample s = f - F (older slots meet zero taps only); all loads are
-    // unconditional from a clamped index (one memory round trip for the lot).
-    constexpr int NHI = GS::HS / kWave, NFI = 2 * G::HH4 / kWave;
-    static_assert(GS::HS % kWave == 0 && (2 * G::HH4) % kWave == 0, "state fills are whole wave loads");
-    v2f st_hv[NHI];
-    float st_fv[NFI], st_gain;
+    // unconditional (one memory round trip for the lot).
+    // (the Hilbert-pair rows -- HH floats per rail, HH even, the leading pad FH of the LDS window even -- move as float pairs, 8 bytes per
+    // lane: pair q of the wave is pair q % (HH4 / 2) of rail q / (HH4 / 2), a rail >= 2 is nobody's; the decimator rows start on odd
+    // words -- 2 (nd - 1) floats per channel, the Q rail nd - 1 floats in -- and move as single floats)
+    constexpr int NHI = GS::HS / kWave, NFP = (G::HH4 + kWave - 1) / kWave, FPR = G::HH4 / 2;
+    static_assert(GS::HS % kWave == 0 && G::HH % 2 == 0 && G::FH % 2 == 0 && G::DLEN % 2 == 0, "state fills: whole wave loads, float pairs");
+    v2f st_hv[NHI], st_fv[NFP];
+    float st_gain;
     uint32_t st_ph0, st_step, st_word;
+    // (one descriptor per row of the channel: the bytes of the row, nothing for a channel past the last one -- zeros, no traffic, never
+    // installed; a lane in front of the row -- history slots that meet zero taps only -- is out of range and reads the zero it needs)
     auto load_state = [&](uint32_t ch) {
         const int ndr = (int)p.nd, Fr = G::HQ4 * M + 1 - ndr;
-        ch = ch < p.channels ? ch : p.channels - 1;               // past the last channel: harmless reload, never installed
-        const float *stI = p.dec_state + (size_t)ch * 2 * (ndr - 1), *stQ = stI + (ndr - 1);
-        const float *stF = p.fir_state + (size_t)ch * 2 * G::HH;
+        const bool real = ch < p.channels;
+        int lane_o = lane;                                            // (opaque: the lane offsets below, hoisted out of the channel loop, would be the
+        asm volatile("" : "+v"(lane_o));                              // kernel's only scratch -- and a kernel with scratch pays ~12 us per launch)
+        const __amdgpu_buffer_rsrc_t rs_dec = make_rsrc(p.dec_state + (size_t)ch * 2 * (ndr - 1), real ? 8u * (uint32_t)(ndr - 1) : 0u);
+        const __amdgpu_buffer_rsrc_t rs_fir = make_rsrc(p.fir_state + (size_t)ch * 2 * G::HH, real ? 8u * (uint32_t)G::HH : 0u);
 #pragma unroll
         for (int j = 0; j < NHI; ++j) {
-            const int s = j * kWave + lane - Fr, sc = s < 0 ? 0 : s;
-            const float xi = st_ld(stI + sc), xq = st_ld(stQ + sc);
-            st_hv[j] = s < 0 ? v2f{ 0.0f, 0.0f } : v2f{ xi, xq };
+            const int o = st_off(4 * (j * kWave + lane_o - Fr));
+            st_hv[j] = v2f{ __uint_as_float(st_ld(rs_dec, o, 0)), __uint_as_float(st_ld(rs_dec, o, 4 * (ndr - 1))) };
         }
 #pragma unroll
-        for (int j = 0; j < NFI; ++j) {
-            const int i = j * kWave + lane;
-            const int rail = i / G::HH4, sidx = i % G::HH4 - G::FH;
-            const float x = st_ld(stF + rail * G::HH + (sidx < 0 ? 0 : sidx));
-            st_fv[j] = sidx < 0 ? 0.0f : x;
+        for (int j = 0; j < NFP; ++j) {
+            const uint32_t q = (uint32_t)(j * kWave) + (uint32_t)lane_o, rail = q / FPR;
+            const int sidx = 2 * (int)(q % FPR) - G::FH;
+            st_fv[j] = st_ld2(rs_fir, sidx < 0 || rail >= 2u ? kStOob : 4 * ((int)rail * G::HH + sidx), 0);
         }
-        st_ph0 = NCO ? p.phase[ch] : 0u;
-        st_step = NCO ? p.step[ch] : 0u;
-        st_gain = p.gain[ch];
-        st_word = p.rerun_flag ? p.rerun_flag[ch] : 0u;           // AUTO: provenance of the channel's state, which hist_ext buffer goes with it
+        const uint32_t one = real ? 4u : 0u;
+        st_ph0 = NCO ? st_ld(make_rsrc(p.phase + ch, one), 0, 0) : 0u;
+        st_step = NCO ? st_ld(make_rsrc(p.step + ch, one), 0, 0) : 0u;
+        st_gain = __uint_as_float(st_ld(make_rsrc(p.gain + ch, one), 0, 0));
+        st_word = p.rerun_flag ? st_ld(make_rsrc(p.rerun_flag + ch, one), 0, 0) : 0u;   // AUTO: provenance of the channel's state, which hist_ext buffer goes with it
     };
     uint32_t prev_prov = kProvExact, prev_buf = 0u, st_word_cur = 0u;
     // SELENITE_ARITH_AUTO: the mixed samples in front of the decimator state go to hist_ext (RxParams), so that a rerun of the NEXT
@@ -419,17 +443,21 @@ __global__ __launch_bounds__(64, 2) void k_ssb_split16(RxParams p, FusedArgs fa,
             mh = amax2(st_hv[j], mh);
         }
 #pragma unroll
-        for (int j = 0; j < NFI; ++j) {
-            const int i = j * kWave + lane;
-            D[(i / G::HH4) * G::DLEN + i % G::HH4] = st_fv[j];
+        for (int j = 0; j < NFP; ++j) {
+            const int q = j * kWave + lane;
+            if (q < 2 * FPR) {
+                D[(q / FPR) * G::DLEN + 2 * (q % FPR)] = st_fv[j].x;
+                D[(q / FPR) * G::DLEN + 2 * (q % FPR) + 1] = st_fv[j].y;
+            }
         }
         b_hist = wave_umax_bits(mh);
         ph0 = st_ph0; step = st_step; gain = st_gain;
         s_cur = 0x7fff;
         gd.n = 0u; gd.nh = 0u;
-        thr_cur = __uint_as_float(st_word & kLvlMask) * p.guard_ratio;     // ("the pass before pass 0": shifted into thr_prev by mix(0))
+        const uint32_t word = __builtin_amdgcn_readfirstlane(st_word);     // (every lane loaded the same word: scalar from here on)
+        thr_cur = __uint_as_float(word & kLvlMask) * p.guard_ratio;        // ("the pass before pass 0": shifted into thr_prev by mix(0))
         thr_prev = 0.0f;
-        prev_prov = (st_word >> kProvShift) & kProvMask; prev_buf = (st_word >> kExtBufShift) & 1u; st_word_cur = st_word;
+        prev_prov = (word >> kProvShift) & kProvMask; prev_buf = (word >> kExtBufShift) & 1u; st_word_cur = word;
         if (ext_on)                                                   // the buffer the state of the call before does NOT point at
             rs_ext = make_rsrc(p.hist_ext + (size_t)(prev_buf ^ 1u) * p.ext_buf_stride + (size_t)c * p.ext_len, p.ext_len * (sizeof(TIn) == 2 ? 4u : 8u));
         if constexpr (NCO == 4) {
@@ -705,12 +733,21 @@ __global__ __launch_bounds__(64, 2) void k_ssb_split16(RxParams p, FusedArgs fa,
         for (int kk = 0; kk < GS::KS; ++kk) demod_piece(kk, au, nvb);
     };
     bool nonfinite = false;                                           // any audio sample of this workgroup NaN / Inf (x * 0 is NaN iff x is)
-    auto store_audio = [&](uint32_t q, const float (&au)[4]) {
+    // tail: the stores behind the pass loop, which the channel's epilogue follows.  A buffer store of more than 8 bytes reads its data
+    // registers for a few cycles after it issues, and a vector instruction that writes one of them right behind it needs wait states
+    // in between.  The compiler inserts them only for stores WITHOUT a scalar-register offset (the documented form of the hazard); on
+    // gfx950 the form with one needs them too: with the epilogue's first instruction (a v_mov of the lane id into the register of au[1])
+    // right behind the last store, the by-2 M instantiation stored lane ids as audio in lanes 12-15 / 28-31 of a workgroup's first
+    // channel, in 4 % of the first calls of an instance (profiles/chan_fixed/README.md).  So these stores carry the pass offset in the
+    // lane offset, the form the compiler guards.  (Inside the loop au is rewritten a matrix stage later.)
+    auto store_audio = [&](uint32_t q, const float (&au)[4], bool tail = false) {
         const float z = __builtin_fmaf(au[3], 0.0f, __builtin_fmaf(au[2], 0.0f, __builtin_fmaf(au[1], 0.0f, au[0] * 0.0f)));
         nonfinite = nonfinite || ((z != z) && (!DEC2 || (uint32_t)lane < pq / 4u));            // (by 2 M: the lanes past the pass hold no output of the chain)
         // (pq < 256: the last lanes hold outputs of the NEXT pass's region, computed from its first samples -- not stored)
         const int vo = (GROUP != 0 || (uint32_t)lane < pq / 4u) ? lane * W::kBytes : 0x40000000;
-        W::store(rs_out, vo, (int)(q * pq) * (W::kBytes / 4), au, ENV != 0, p.q15_round);      // (ENV: phase 1 of the global-gain call -- the gain pass reads this audio back: default policy, known at compile time)
+        const int so = (int)(q * pq) * (W::kBytes / 4);
+        if (tail) W::store(rs_out, vo + so, 0, au, ENV != 0, p.q15_round);
+        else W::store(rs_out, vo, so, au, ENV != 0, p.q15_round);      // (ENV: phase 1 of the global-gain call -- the gain pass reads this audio back: default policy, known at compile time)
         if constexpr (GROUP == 16 && ENV != 0) {
             {
                 const float m = row16_fmax(fmaxf(fmaxf(fabsf(au[0]), fabsf(au[1])), fmaxf(fabsf(au[2]), fabsf(au[3]))));
@@ -764,55 +801,63 @@ __global__ __launch_bounds__(64, 2) void k_ssb_split16(RxParams p, FusedArgs fa,
             dwrite();
             lds_order();
         }
-        store_audio(npass - 2, au);
+        store_audio(npass - 2, au, true);
         load_state(c_nx);                                             // the next channel's state, under this channel's last demodulator pass
         gd.thr = thr_cur; gd.thr_h = fmaxf(thr_cur, thr_prev);
         gd.hist = npass == 1 ? hist_mask : 0ull;
         demod(au, (int)(tail_out / (4u * (uint32_t)group)));          // DSP blocks of the last pass that exist
-        store_audio(npass - 1, au);
+        store_audio(npass - 1, au, true);
 
         // ---- parity guard: count (per-channel words: no atomics); SELENITE_ARITH_AUTO: a guarded channel keeps its pre-call
         // state and raises its rerun flag (the flag of every channel is rewritten every call) ----
         const bool keep_state = gd.n != 0u && p.rerun_flag != nullptr;   // wave-uniform
-        if (lane == 0) {
-            if (gd.n != 0u && p.guard_ch) { p.guard_ch[c] = sat_add_u32(p.guard_ch[c], gd.n); p.guard_calls[c] = sat_add_u32(p.guard_calls[c], 1u); }
-            // handover blocks the rerun cannot repair: the call before stayed on the matrix kernel and left no hist_ext (a short call)
-            // (or left them but the repair has been switched off since)
-            if (keeps && gd.nh != 0u && (prev_prov == kProvSplit || (prev_prov == kProvSplitExt && !p.hist_ext)) && p.guard_hand) p.guard_hand[c] = sat_add_u32(p.guard_hand[c], gd.nh);      // (AM reads no history)
-            if (p.rerun_flag) {
-                const uint32_t kept = !keeps ? (((prev_prov == kProvExact ? kProvExact : kProvSplit) << kProvShift) | (prev_buf << kExtBufShift))      // (no samples: the format bit is void)
-                                              : (((ext_on ? kProvSplitExt : kProvSplit) << kProvShift) | ((prev_buf ^ 1u) << kExtBufShift) |
-                                                 (ext_on && sizeof(TIn) == 2 ? kExtQ15 : 0u));
-                // (kept on the matrix kernel: the level of the last pass goes with the state -- the first blocks of the next call read
-                // Hilbert-pair history computed from those samples; rounded up to the 24 bits the word has room for)
-                p.rerun_flag[c] = keep_state ? (kFlagRerun | (st_word_cur & (kExtQ15 | (kProvMask << kProvShift) | (1u << kExtBufShift))))
-                                             : (kept | ((b_last + 0xFFu) & kLvlMask));
-            }
+        // (every condition below is wave-uniform and every word is computed by the whole wave from wave-uniform values: one store per
+        // word, which the range check keeps to lane 0 -- no exec-masked block)
+        int lane_o = lane;                                            // (opaque, as in load_state)
+        asm volatile("" : "+v"(lane_o));
+        const int v_l0 = lane_o == 0 ? 0 : kStOob;
+        auto word_add = [&](uint32_t *w, uint32_t n) {                // (rare: a channel with guarded blocks)
+            const __amdgpu_buffer_rsrc_t rs = make_rsrc(w + c, 4u);
+            st_st(rs, v_l0, 0, sat_add_u32(st_ld(rs, 0, 0), n));
+        };
+        if (gd.n != 0u && p.guard_ch) { word_add(p.guard_ch, gd.n); word_add(p.guard_calls, 1u); }
+        // handover blocks the rerun cannot repair: the call before stayed on the matrix kernel and left no hist_ext (a short call)
+        // (or left them but the repair has been switched off since)
+        if (keeps && gd.nh != 0u && (prev_prov == kProvSplit || (prev_prov == kProvSplitExt && !p.hist_ext)) && p.guard_hand) word_add(p.guard_hand, gd.nh);      // (AM reads no history)
+        if (p.rerun_flag) {
+            const uint32_t kept = !keeps ? (((prev_prov == kProvExact ? kProvExact : kProvSplit) << kProvShift) | (prev_buf << kExtBufShift))      // (no samples: the format bit is void)
+                                          : (((ext_on ? kProvSplitExt : kProvSplit) << kProvShift) | ((prev_buf ^ 1u) << kExtBufShift) |
+                                             (ext_on && sizeof(TIn) == 2 ? kExtQ15 : 0u));
+            // (kept on the matrix kernel: the level of the last pass goes with the state -- the first blocks of the next call read
+            // Hilbert-pair history computed from those samples; rounded up to the 24 bits the word has room for)
+            st_st(make_rsrc(p.rerun_flag + c, 4u), v_l0, 0,
+                  keep_state ? (kFlagRerun | (st_word_cur & (kExtQ15 | (kProvMask << kProvShift) | (1u << kExtBufShift))))
+                             : (kept | ((b_last + 0xFFu) & kLvlMask)));
         }
         // ---- streaming state of the channel back to HBM (exact f32) ----
         lds_order();
         if (!keep_state) {
             const int ndr = (int)p.nd, Fr = G::HQ4 * M + 1 - ndr;
-            float *stI = p.dec_state + (size_t)c * 2 * (ndr - 1), *stQ = stI + (ndr - 1);
+            const __amdgpu_buffer_rsrc_t rs_dec = make_rsrc(p.dec_state + (size_t)c * 2 * (ndr - 1), 8u * (uint32_t)(ndr - 1));
 #pragma unroll
             for (int j = 0; j < GS::HS / kWave; ++j) {
-                const int s = j * kWave + lane - Fr;
-                const v2f h = Hf[j * kWave + lane];
-                if (s >= 0) { st_st(stI + s, h.x); st_st(stQ + s, h.y); }
+                const int o = st_off(4 * (j * kWave + lane_o - Fr));
+                const v2f h = Hf[j * kWave + lane_o];
+                st_st(rs_dec, o, 0, __float_as_uint(h.x));
+                st_st(rs_dec, o, 4 * (ndr - 1), __float_as_uint(h.y));
             }
-        }
-        if (keeps) {                                                  // AM never ran the Hilbert pair: its state stays (FM keeps the delay lines running)
-            int lane_o = lane;                                        // (opaque: the per-lane 64-bit offsets of this loop, hoisted out of the channel
-            asm volatile("" : "+v"(lane_o));                          // loop, were the kernel's only scratch -- and a kernel with scratch pays ~12 us per launch)
-            if (!keep_state)
-                for (int i = lane_o; i < 2 * G::HH4; i += kWave) {
-                    const int rail = i / G::HH4, mi = i % G::HH4, s = mi - G::FH;
-                    if (s >= 0) st_st(p.fir_state + ((size_t)c * 2 + rail) * G::HH + s, D[rail * G::DLEN + tail_out + mi]);
+            if (keeps) {                                              // AM never ran the Hilbert pair: its state stays (FM keeps the delay lines running)
+                const __amdgpu_buffer_rsrc_t rs_fir = make_rsrc(p.fir_state + (size_t)c * 2 * G::HH, 8u * (uint32_t)G::HH);
+#pragma unroll
+                for (int j = 0; j < NFP; ++j) {
+                    const uint32_t q = (uint32_t)(j * kWave) + (uint32_t)lane_o, rail = q / FPR, mi = 2u * (q % FPR);
+                    const int sidx = (int)mi - G::FH;
+                    const float *d = D + (rail < 2u ? rail : 1u) * G::DLEN + tail_out + mi;
+                    st_st2(rs_fir, sidx < 0 || rail >= 2u ? kStOob : 4 * ((int)rail * G::HH + sidx), 0, v2f{ d[0], d[1] });
                 }
-        }
-        if (lane == 0 && !keep_state) {
-            if constexpr (NCO != 0) p.phase[c] = ph0 + p.block_size * step;
-            if (p.agc) p.gain[c] = gain;
+            }
+            if constexpr (NCO != 0) st_st(make_rsrc(p.phase + c, 4u), v_l0, 0, ph0 + p.block_size * step);
+            if (p.agc) st_st(make_rsrc(p.gain + c, 4u), v_l0, 0, __float_as_uint(gain));
         }
         c = c_nx;
         if (c >= p.channels) break;
