@@ -288,6 +288,61 @@ typedef struct selenite_rx_nb_state_view {
     uint64_t *bursts;
 } selenite_rx_nb_state_view;
 
+/* ---- I/Q correction: DC offset, gain and phase imbalance (on the raw input I/Q behind the
+ * spectrum tap and in front of the noise blanker; off by default) ---------------------------------------------------------------------
+ * A quadrature sampling detector in front of a stereo codec leaves a DC offset on each rail (a carrier in the passband) and a gain and
+ * phase mismatch between the rails (a mirror image of every signal on the other sideband) that no Hilbert pair behind it removes.  Every
+ * mode, every arith mode.  The call's input (int16 slots seen through arm_q15_to_float) is cut into frames of `frame` consecutive complex
+ * samples, I[n] = x[2n], Q[n] = x[2n + 1]; frame divides cfg.block and every call is a whole number of DSP blocks, so nothing is left
+ * pending.  Per channel four floats of state, dc_i, dc_q, p, g (dc_i_init, dc_q_init, p_init, g_init after set_iqc and reset), and one
+ * counter, held (0).  Per frame, every operation rounded to f32, no contraction, denormals kept:
+ *   correct, with the coefficients in front of the frame:
+ *     i[n] = I[n] - dc_i, q[n] = Q[n] - dc_q            BasicMathFunctions/arm_offset_f32.c:145 with the negated offset: the same bits
+ *     t[n] = i[n] * p                                   BasicMathFunctions/arm_scale_f32.c:148
+ *     u[n] = q[n] - t[n]                                BasicMathFunctions/arm_sub_f32.c:129
+ *     Iout[n] = i[n], Qout[n] = u[n] * g                arm_scale_f32
+ *   DC estimate (dc_alpha > 0):
+ *     mi = arm_mean_f32(I, frame), mq likewise          StatisticsFunctions/arm_mean_f32.c:67-120: s = 0; s = s + I[n], n ascending; s / frame
+ *     dc_i = dc_i + dc_alpha * (mi - dc_i)              difference, product, sum each rounded (the AGC's form); a rail whose mean is not
+ *                                                       finite keeps its dc
+ *   imbalance estimate (alpha > 0), on the i, q above:
+ *     pii = arm_power_f32(i), pqq = arm_power_f32(q)    StatisticsFunctions/arm_power_f32.c:86-117: sum = sum + in * in, n ascending
+ *     piq = arm_dot_prod_f32(i, q)                      BasicMathFunctions/arm_dot_prod_f32.c:85-112: sum = sum + a * b, n ascending
+ *     a = piq / pii; r = pqq - a * piq; b = arm_sqrt_f32(pii / r)        Include/arm_math.h:5726-5742: sqrtf, correctly rounded
+ *     valid: pii > min_power && pii <= FLT_MAX && r > min_power && r <= FLT_MAX          (a NaN anywhere: not valid)
+ *     valid:     a = a < -p_max ? -p_max : (a > p_max ? p_max : a);  b = b < g_min ? g_min : (b > g_max ? g_max : b), g_min = 1.0f / g_max
+ *                p = p + alpha * (a - p);  g = g + alpha * (b - g)
+ *     not valid: p and g stay, held += 1
+ *   alpha == 0: no estimate, held does not move (manual calibration: p_init / g_init, or selenite_rx_set_iqc_state).
+ * The estimates read the raw input and the dc in front of the frame, never the corrected output.  The corrected samples are always f32, in
+ * a buffer of the instance; the rest of the call (the noise blanker, then the chain) reads that in place of the caller's input, and the
+ * spectrum tap keeps reading the caller's own.  int16 slots become f32 in, int16 out: the audio words are arm_float_to_q15 of the f32
+ * call's audio, bit for bit in SELENITE_ARITH_CMSIS and _FMA and within the int16 bar of the arith mode otherwise.  Bit-exact against that
+ * composition.  The stage never raises SELENITE_RX_NANINF. */
+typedef struct selenite_rx_iqc_config {
+    uint32_t struct_size;     /* = sizeof(selenite_rx_iqc_config) (this struct's own growth path) */
+    uint32_t frame;           /* F: 32, 64 or 128, and a divisor of cfg.block; anything else is a SELENITE_RX_LENGTH_ERROR */
+    float alpha;              /* 0 .. 1; 0: p and g are not estimated */
+    float dc_alpha;           /* 0 .. 1; 0: dc_i and dc_q are not estimated */
+    float p_max;              /* finite, 0 < p_max <= 1 */
+    float g_max;              /* finite, >= 1 */
+    float min_power;          /* finite, >= 0 */
+    float p_init;             /* -p_max .. p_max */
+    float g_init;             /* 1 / g_max .. g_max */
+    float dc_i_init;          /* finite */
+    float dc_q_init;          /* finite */
+} selenite_rx_iqc_config;
+
+/* The stage's whole state, each [channels]: dc_i, dc_q, p, g; held: frames whose imbalance estimate was not valid since set_iqc / reset.
+ * NULL members are skipped. */
+typedef struct selenite_rx_iqc_state_view {
+    float *dc_i;
+    float *dc_q;
+    float *p;
+    float *g;
+    uint64_t *held;
+} selenite_rx_iqc_state_view;
+
 typedef struct selenite_rx_instance selenite_rx_instance;  /* opaque; state lives in HBM */
 
 /* ---- instance life cycle ------------------------------------------------------------- */
@@ -476,6 +531,22 @@ int selenite_rx_set_nb(selenite_rx_instance *S, const selenite_rx_nb_config *nb)
 /* Host copies of the state.  Drains the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the blanker is off. */
 int selenite_rx_get_nb_state(selenite_rx_instance *S, const selenite_rx_nb_state_view *dst);
 int selenite_rx_set_nb_state(selenite_rx_instance *S, const selenite_rx_nb_state_view *src);
+
+/* ---- I/Q correction ---------------------------------------------------------------------- */
+
+/* Sets the I/Q correction for every channel (selenite_rx_iqc_config), or removes it (iqc == NULL).  Sets the stage's state to the config's
+ * inits and touches nothing else.  A bad field (frame: SELENITE_RX_LENGTH_ERROR, any other: SELENITE_RX_ARGUMENT_ERROR) leaves the
+ * instance as it was, a working stage included.  SELENITE_RX_DEVICE_ERROR is different: the old stage is released before the new state
+ * rows are allocated, so a failed allocation leaves the instance with NO stage (as after iqc == NULL), its chain untouched.
+ * selenite_rx_set_mode, _set_nr, _set_out, _set_spectrum and _set_nb leave it alone;
+ * selenite_rx_reset returns the four floats to their inits and held to zero.  Every process entry point that has input runs it once per
+ * call, in front of the noise blanker (f32 and int16 slots, device and host pointers, the timing calls, global phase 1,
+ * selenite_rx_global_process_f32_device -- not phase 2, not the roof timing calls).  The corrected copy lives in a buffer of the instance,
+ * grown by the first call that needs it.  With the stage off no launch, byte, allocation or output of any call changes. */
+int selenite_rx_set_iqc(selenite_rx_instance *S, const selenite_rx_iqc_config *iqc);
+/* Host copies of the state.  Drains the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the stage is off. */
+int selenite_rx_get_iqc_state(selenite_rx_instance *S, const selenite_rx_iqc_state_view *dst);
+int selenite_rx_set_iqc_state(selenite_rx_instance *S, const selenite_rx_iqc_state_view *src);
 
 void *selenite_rx_device_alloc(size_t bytes);          /* hipMalloc; NULL on failure */
 void  selenite_rx_device_free(void *dptr);

@@ -1,6 +1,6 @@
 // rx_dispatch.hip -- the one dispatcher behind every process entry point: which kernels serve a call, over which channels
-// (ChanRange), from which stream positions (CallStart).  The four stages hook in here and nowhere else: the spectrum tap and the noise
-// blanker in front of the chain, NLMS in front of the AGC, the output stage behind the chain.
+// (ChanRange), from which stream positions (CallStart).  The five stages hook in here and nowhere else: the spectrum tap, the I/Q correction
+// and the noise blanker in front of the chain, NLMS in front of the AGC, the output stage behind the chain.
 #include "rx_host.h"
 
 #include <dlfcn.h>
@@ -115,6 +115,9 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
     // a global gain get their input converted once, up front -- arm_q15_to_float over the whole buffer, the very operation the fused
     // int16 load performs -- and run as an f32-input call whose gain pass stores int16; round 2 left them to the generic kernels)
     // (the NLMS stage the same way: the fused kernel leaves un-scaled f32 audio, the stage runs in place on it, the AGC pass stores)
+    // (and int16 slots behind the I/Q correction, whose copy is f32: f32 in, int16 out -- the fused kernel with its AGC off into the f32
+    // scratch, k_agc_generic applies the AGC and stores int16)
+    const bool mixed = !src_q15 && dst_q15;
     const bool fusable = phase != kPhase2 && !S->force_generic;
     const bool ssb_fused = fusable && on_ssb_fused(S);
     const bool cw_fused = fusable && cw_fused_ok(g, block_size) && cw_strides_ok(p.in_stride, p.out_stride);    // (wider strides: the generic kernels)
@@ -131,7 +134,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
         }
     }
     float *audio = (float *)dst;      // un-scaled audio: dst itself when dst is f32, else scratch
-    if (dst_q15 && (global || nr || !(ssb_fused || cw_fused))) {
+    if (dst_q15 && (global || nr || mixed || !(ssb_fused || cw_fused))) {
         const size_t need = (size_t)g.channels * p.out_stride * sizeof(float);
         int rc = ensure(S, (void **)&S->d_scratch, &S->scratch_bytes, need);
         if (rc) return rc;
@@ -181,7 +184,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
         }
         void *fdst = dst;
         bool fq15 = dst_q15;
-        if (global || nr) {
+        if (global || nr || mixed) {
             pf.agc = 0; fdst = audio; fq15 = false;
             pf.out_cached = 1;                            // phase 2 (and, without block maxima from the kernel, the envelope fold) reads this audio back
             if (d.env_part) {                             // the kernel leaves the block maxima of every channel behind: folded below
@@ -194,7 +197,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
         }
         if (ssb_fused) HIPCHK(S, launch_fused(S->plan, pf, d, src, src_q15, fdst, fq15, S->delay_index, st));
         else HIPCHK(S, launch_cw_fused(pf, src, src_q15, fdst, fq15, st));
-        if (!global && !nr) return SELENITE_RX_SUCCESS;
+        if (!global && !nr && !mixed) return SELENITE_RX_SUCCESS;
     }
 
     // generic path: front -> [biquad] -> AGC / convert
@@ -242,7 +245,7 @@ static int run_chain_core(selenite_rx_instance *S, ChanRange r, uint32_t phase_n
     const bool ssb = phase != kPhase2 && on_ssb_fused(S);
     if (ssb && S->plan.sel.btab16)
         if (int rc = ensure_hist_ext(S)) return rc;
-    SelCall c = call_facts(S, block_size, dst_q15);
+    SelCall c = call_facts(S, block_size, src_q15 && dst_q15);      // (f32 in, int16 out -- behind the I/Q correction -- is decided as the f32 call it runs as)
     const Decision d = select(g, ssb ? S->plan.sel : SelPlan{}, c);
     if (!d.first) return run_part(S, r, d, phase_now, src, src_q15, dst, dst_q15, block_size, phase, ext_env, block_size, nout);
     const uint32_t bs1 = d.first;
@@ -265,6 +268,11 @@ int srx::run_chain(selenite_rx_instance *S, ChanRange r, CallStart at, const voi
     if (S->out.on && phase != kAll) return fail(S, SELENITE_RX_ARGUMENT_ERROR, "the split global-gain calls exchange audio at the decimated rate: not with an output stage");
     if (S->spec.len && phase != kPhase2)
         if (int rc = S->spec.run(S, r, at.spec_pos, src, src_q15, block_size)) return rc;
+    // step 0b2: from here on the call reads the corrected f32 copy of the input (the tap above has read the caller's own)
+    if (S->iqc.frame && phase != kPhase2) {
+        if (int rc = S->iqc.run(S, r, src, src_q15, block_size, &src)) return rc;
+        src_q15 = false;
+    }
     // step 0c: from here on the chain reads the blanked copy of the input (the tap above has read the caller's own)
     if (S->nb.frame && phase != kPhase2)
         if (int rc = S->nb.run(S, r, src, src_q15, block_size, &src)) return rc;
@@ -332,7 +340,8 @@ extern "C" int selenite_rx_global_process_f32_device(selenite_rx_instance *S, co
     if (S->out.on && (rc = S->out.audio_buffer(S, r, blockSize, &audio))) return rc;
     if (S->spec.len && (rc = S->spec.run(S, r, at.spec_pos, dSrcIQ, false, blockSize))) return rc;
     const void *in = dSrcIQ;
-    if (S->nb.frame && (rc = S->nb.run(S, r, dSrcIQ, false, blockSize, &in))) return rc;
+    if (S->iqc.frame && (rc = S->iqc.run(S, r, in, false, blockSize, &in))) return rc;
+    if (S->nb.frame && (rc = S->nb.run(S, r, in, false, blockSize, &in))) return rc;
     rc = run_chain_core(S, r, at.phase, in, false, audio, false, blockSize, kPhase1, S->d_env);
     if (rc) return rc;
     if (rccl_comm) {                                        // NULL: single rank, nothing to exchange

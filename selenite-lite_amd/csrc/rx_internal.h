@@ -257,6 +257,31 @@ struct __attribute__((visibility("hidden"))) NbStage {
     int run(selenite_rx_instance *S, ChanRange r, const void *src, bool src_q15, uint32_t block_size, const void **blanked_src);
 };
 
+// ---- I/Q correction (rx_iqc.hip): DC offset, gain and phase imbalance of the raw input, estimated per frame and removed ----
+struct IqcParams {
+    uint32_t channels;     // channels of this launch (a ChanRange: the five state rows are offset to it)
+    uint32_t block_size;   // input samples per channel in this call = complex samples between consecutive channels of source and copy
+    float alpha, dc_alpha; // 0: that estimate is off
+    float p_max, g_min, g_max, min_power;
+    float *dc_i, *dc_q;    // [C] each
+    float *p, *g;          // [C] each
+    uint64_t *held;        // [C] frames whose imbalance estimate was not valid so far
+};
+hipError_t launch_iqc(const IqcParams &q, uint32_t frame, const void *src, bool src_q15, float *dst, hipStream_t st);
+// the stage's part of the instance (selenite_rx_set_iqc): frame = 0: no stage, no buffers
+struct __attribute__((visibility("hidden"))) IqcStage {
+    uint32_t frame = 0;
+    float alpha = 0.0f, dc_alpha = 0.0f, p_max = 0.0f, g_min = 0.0f, g_max = 0.0f, min_power = 0.0f;
+    float p_init = 0.0f, g_init = 0.0f, dc_i_init = 0.0f, dc_q_init = 0.0f;
+    float *d_dc_i = nullptr, *d_dc_q = nullptr, *d_p = nullptr, *d_g = nullptr;      // [channels] each
+    uint64_t *d_held = nullptr;                             // [channels]
+    float *d_buf = nullptr; size_t buf_bytes = 0;           // the corrected copy of a call's input, [channels of the launch][blockSize][2] f32
+    void release();                                         // frees the buffers: no stage
+    int init_state(selenite_rx_instance *S);                // the state set_iqc leaves
+    // one launch on the instance's stream: `src` (f32, or int16 as it is) -> d_buf (always f32), grown to the launch; *corrected_src = d_buf
+    int run(selenite_rx_instance *S, ChanRange r, const void *src, bool src_q15, uint32_t block_size, const void **corrected_src);
+};
+
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
     SelPlan sel;                  // what select() reads: the shape (kind 0 = none), dense or not, which operands exist (rx_select.h)
@@ -353,6 +378,7 @@ struct selenite_rx_instance {
     srx::NrStage nr;                   // NLMS noise reduction / automatic notch, in front of the AGC (rx_nlms.hip)
     srx::OutStage out;                 // audio output stage, behind the chain (rx_out.hip)
     srx::SpecStage spec;               // spectrum tap, in front of the chain (rx_spectrum.hip)
+    srx::IqcStage iqc;                 // I/Q correction, between the spectrum tap and the noise blanker (rx_iqc.hip)
     srx::NbStage nb;                   // impulse noise blanker, between the spectrum tap and the chain (rx_nb.hip)
     int status = SELENITE_RX_SUCCESS;
     std::string err;

@@ -93,6 +93,18 @@ class NbStateView(C.Structure):
     _fields_ = [("level", f32p), ("blanked", u64p), ("bursts", u64p)]
 
 
+class IqcConfig(C.Structure):
+    """struct selenite_rx_iqc_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("frame", C.c_uint32), ("alpha", C.c_float), ("dc_alpha", C.c_float), ("p_max", C.c_float),
+                ("g_max", C.c_float), ("min_power", C.c_float), ("p_init", C.c_float), ("g_init", C.c_float), ("dc_i_init", C.c_float),
+                ("dc_q_init", C.c_float)]
+
+
+class IqcStateView(C.Structure):
+    """struct selenite_rx_iqc_state_view."""
+    _fields_ = [("dc_i", f32p), ("dc_q", f32p), ("p", f32p), ("g", f32p), ("held", u64p)]
+
+
 # every symbol include/selenite_rx.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "selenite_rx_init", "selenite_rx_free", "selenite_rx_set_mode", "selenite_rx_status",
@@ -115,6 +127,7 @@ ABI_SYMBOLS = [
     "selenite_rx_set_spectrum", "selenite_rx_get_spectrum", "selenite_rx_spectrum_device", "selenite_rx_get_spectrum_state",
     "selenite_rx_set_spectrum_state", "selenite_rx_spectrum_twiddles", "selenite_rx_design_window",
     "selenite_rx_set_nb", "selenite_rx_get_nb_state", "selenite_rx_set_nb_state",
+    "selenite_rx_set_iqc", "selenite_rx_get_iqc_state", "selenite_rx_set_iqc_state",
 ]
 
 class TxConfig(C.Structure):
@@ -255,6 +268,10 @@ def lib():
             L.selenite_rx_set_nb.argtypes = [vp, C.POINTER(NbConfig)]
             L.selenite_rx_get_nb_state.argtypes = [vp, C.POINTER(NbStateView)]
             L.selenite_rx_set_nb_state.argtypes = [vp, C.POINTER(NbStateView)]
+        if hasattr(L, "selenite_rx_set_iqc"):               # (an older build named by SELENITE_RX_LIB lacks the I/Q correction)
+            L.selenite_rx_set_iqc.argtypes = [vp, C.POINTER(IqcConfig)]
+            L.selenite_rx_get_iqc_state.argtypes = [vp, C.POINTER(IqcStateView)]
+            L.selenite_rx_set_iqc_state.argtypes = [vp, C.POINTER(IqcStateView)]
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -828,6 +845,52 @@ class Rx:
         rc = self.L.selenite_rx_set_nb_state(self.h, C.byref(v))
         if rc:
             raise RxError(rc, "selenite_rx_set_nb_state")
+
+    # -- I/Q correction (selenite_rx_set_iqc) ----------------------------------------------------
+    IQC_FLOATS = ("dc_i", "dc_q", "p", "g")
+
+    def set_iqc(self, frame=64, alpha=1.0 / 64, dc_alpha=1.0 / 16, p_max=0.25, g_max=1.5, min_power=1e-12, p_init=0.0, g_init=1.0,
+                dc_i_init=0.0, dc_q_init=0.0):
+        """Put the I/Q correction (DC offset, gain and phase imbalance) on the raw input of every channel, in front of the noise blanker, or
+        remove it (frame=None).  Sets the stage's state to the inits.  Raises RxError on a bad field; the instance is then left as it was."""
+        old, self._iqc = getattr(self, "_iqc", None), None
+        if frame is None:
+            rc = self.L.selenite_rx_set_iqc(self.h, None)
+        else:
+            g = IqcConfig()
+            g.struct_size, g.frame = C.sizeof(IqcConfig), int(frame)
+            g.alpha, g.dc_alpha, g.p_max, g.g_max, g.min_power = float(alpha), float(dc_alpha), float(p_max), float(g_max), float(min_power)
+            g.p_init, g.g_init, g.dc_i_init, g.dc_q_init = float(p_init), float(g_init), float(dc_i_init), float(dc_q_init)
+            rc = self.L.selenite_rx_set_iqc(self.h, C.byref(g))
+        if rc in (ARGUMENT_ERROR, LENGTH_ERROR):
+            self._iqc = old
+        if rc:
+            raise RxError(rc, self.L.selenite_rx_error_string(None).decode() if rc in (ARGUMENT_ERROR, LENGTH_ERROR) else self.error())
+        self._iqc = int(frame) if frame is not None else None
+
+    def iqc_state(self):
+        """dict(dc_i, dc_q, p, g [channels] f32, held [channels] u64); drains the stream"""
+        if getattr(self, "_iqc", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the I/Q correction is off")
+        c = self.cfg.channels
+        a = {k: np.zeros(c, np.float32) for k in self.IQC_FLOATS}
+        a["held"] = np.zeros(c, np.uint64)
+        v = IqcStateView(*([_fp(a[k]) for k in self.IQC_FLOATS] + [a["held"].ctypes.data_as(u64p)]))
+        rc = self.L.selenite_rx_get_iqc_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_iqc_state")
+        return a
+
+    def set_iqc_state(self, d):
+        if getattr(self, "_iqc", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the I/Q correction is off")
+        a = {k: np.ascontiguousarray(d[k], np.uint64 if k == "held" else np.float32) for k in d}
+        for k in a:
+            assert a[k].shape == (self.cfg.channels,), (k, a[k].shape)
+        v = IqcStateView(*([_fp(a[k]) if k in a else None for k in self.IQC_FLOATS] + [a["held"].ctypes.data_as(u64p) if "held" in a else None]))
+        rc = self.L.selenite_rx_set_iqc_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_set_iqc_state")
 
     def close(self):
         if self.h:
