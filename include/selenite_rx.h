@@ -29,7 +29,9 @@
  *   -> arm_sub_f32 / arm_add_f32 (USB / LSB)   [AM: arm_cmplx_mag_f32]
  *   -> arm_biquad_cascade_df1_f32 (CW narrow filter)
  *   -> [optional: arm_lms_norm_f32 noise reduction / automatic notch, selenite_rx_set_nr]
+ *   -> [optional: arm_power_f32 per DSP block -> level meter -> squelch decision, selenite_rx_set_meter]
  *   -> arm_abs_f32 + arm_max_f32 -> gain law -> arm_scale_f32 (AGC)
+ *   -> [optional: the squelch gate: closed DSP blocks leave as zeros, selenite_rx_set_meter with gate = 1]
  *   -> [optional: arm_fir_interpolate_f32 back to the slot rate, mono / stereo frames, selenite_rx_set_out]
  */
 #ifndef SELENITE_RX_H
@@ -343,6 +345,55 @@ typedef struct selenite_rx_iqc_state_view {
     uint64_t *held;
 } selenite_rx_iqc_state_view;
 
+/* ---- signal-level meter and squelch (on the un-scaled audio in front of the AGC, the gate
+ * behind it; off by default) -----------------------------------------------------------------------------------------------------------
+ * How strong is the signal in a channel's passband, and is there one at all: agc_gain is the AGC's control variable, not a measurement, and
+ * the spectrum tap shows the band in front of the NCO.  Every mode, every arith mode.  Per channel and per DSP block of n = block / decim
+ * UN-SCALED audio samples x -- the demodulator's output, behind the CW filter and behind NLMS when that is on, in front of the AGC.  Per
+ * channel: level (f32; level_init after set_meter and reset), open (u32, 0 / 1; 0), hold (u32; 0), opens (u64; 0), open_blocks (u64; 0).
+ * Per block, every operation rounded to f32, no contraction, denormals kept:
+ *   pw = arm_power_f32(x, n)            StatisticsFunctions/arm_power_f32.c:64-125: sum = +0.0f; sum = sum + in * in, ascending (product
+ *                                       rounded, then the sum)
+ *   ms = pw / (float)n                  correctly rounded division (n is any block / decim, e.g. 24: not always a power of two)
+ *   ms <= FLT_MAX (false for NaN):      r = ms > level ? attack : decay;  d = ms - level;  level = level + r * d      (the AGC's form)
+ *   otherwise:                          level stays
+ *   v = level
+ *   want_open  = sense == ABOVE ? v > open_level  : v < open_level
+ *   want_close = sense == ABOVE ? v < close_level : v > close_level
+ *   if (!open)           { if (want_open) { open = 1; hold = hang; opens += 1; } }
+ *   else if (want_close) { if (hold == 0) open = 0; else hold -= 1; }
+ *   else                   hold = hang;
+ *   open_blocks += open
+ * SELENITE_RX_SQ_ABOVE is a carrier / level squelch; SELENITE_RX_SQ_BELOW a noise squelch, which FM needs (a quieted discriminator means a
+ * signal).  The hysteresis is close_level against open_level; hang is the number of consecutive closing blocks the gate survives.
+ * gate == 1: a block whose open is 0 AFTER its update leaves the call as +0.0f (int16 slots: 0), BEHIND the AGC: the AGC itself runs on the
+ * un-scaled audio of every block as it does without the stage -- gain, the agc_global envelope and all chain state are bit for bit those
+ * of the same call without the stage.  gate == 0: meter only, the audio is untouched.  With an output stage the gate sits in front of the
+ * interpolator, whose FIR rings the edge out.  The level is a mean square, linear: CMSIS-DSP 1.5.3 has no logarithm (the spectrum tap's
+ * rule).  Bit-exact given its input in every arith mode.  The stage never raises or clears SELENITE_RX_NANINF. */
+#define SELENITE_RX_SQ_ABOVE 0
+#define SELENITE_RX_SQ_BELOW 1
+typedef struct selenite_rx_meter_config {
+    uint32_t struct_size;     /* = sizeof(selenite_rx_meter_config) (this struct's own growth path) */
+    uint32_t sense;           /* SELENITE_RX_SQ_* */
+    uint32_t gate;            /* 0: meter only; 1: closed blocks leave as zeros */
+    uint32_t hang;            /* 0 .. 65535 */
+    float attack;             /* 0 < attack <= 1 */
+    float decay;              /* 0 < decay <= 1 */
+    float open_level;         /* finite, >= 0 */
+    float close_level;        /* finite, >= 0; ABOVE: close_level <= open_level; BELOW: close_level >= open_level */
+    float level_init;         /* finite, >= 0 */
+} selenite_rx_meter_config;
+
+/* The stage's whole state, each [channels].  NULL members are skipped. */
+typedef struct selenite_rx_meter_state_view {
+    float *level;
+    uint32_t *open;
+    uint32_t *hold;
+    uint64_t *opens;          /* closed -> open transitions since set_meter / reset */
+    uint64_t *open_blocks;    /* DSP blocks that ended open since set_meter / reset */
+} selenite_rx_meter_state_view;
+
 typedef struct selenite_rx_instance selenite_rx_instance;  /* opaque; state lives in HBM */
 
 /* ---- instance life cycle ------------------------------------------------------------- */
@@ -547,6 +598,26 @@ int selenite_rx_set_iqc(selenite_rx_instance *S, const selenite_rx_iqc_config *i
 /* Host copies of the state.  Drains the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the stage is off. */
 int selenite_rx_get_iqc_state(selenite_rx_instance *S, const selenite_rx_iqc_state_view *dst);
 int selenite_rx_set_iqc_state(selenite_rx_instance *S, const selenite_rx_iqc_state_view *src);
+
+/* ---- signal-level meter and squelch ------------------------------------------------------- */
+
+/* Sets the meter for every channel (selenite_rx_meter_config), or removes it (m == NULL).  Sets the stage's state to level_init, closed,
+ * counters zero, and touches nothing else.  A bad field (SELENITE_RX_ARGUMENT_ERROR) leaves the instance as it was, a working stage
+ * included.  SELENITE_RX_DEVICE_ERROR is different: the old stage is released before the new state rows are allocated, so a failed
+ * allocation leaves the instance with NO stage (as after m == NULL), its chain untouched.  selenite_rx_set_mode, _set_nr, _set_out,
+ * _set_spectrum, _set_nb and _set_iqc leave it alone; selenite_rx_reset returns it to its state after set_meter.  Every process entry
+ * point runs it once per call (f32 and int16 slots, device and host pointers, the timing calls, selenite_rx_global_process_f32_device;
+ * the split pair: the meter in global phase 1, the gate in phase 2, from the gate bytes phase 1 left in a buffer of the instance).  With
+ * the stage on, the fused kernels run with their own AGC off and the generic AGC kernel finishes the call, as with NLMS.  With the stage
+ * off no launch, byte, allocation or output of any call changes. */
+int selenite_rx_set_meter(selenite_rx_instance *S, const selenite_rx_meter_config *m);
+/* Host copies of the state.  Drains the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the stage is off. */
+int selenite_rx_get_meter_state(selenite_rx_instance *S, const selenite_rx_meter_state_view *dst);
+int selenite_rx_set_meter_state(selenite_rx_instance *S, const selenite_rx_meter_state_view *src);
+/* The level and open rows themselves (device memory, [channels] each), for a consumer on the instance's stream; valid until the next
+ * selenite_rx_set_meter / selenite_rx_free.  NULL while the stage is off. */
+const float *selenite_rx_meter_level_device(const selenite_rx_instance *S);
+const uint32_t *selenite_rx_meter_open_device(const selenite_rx_instance *S);
 
 void *selenite_rx_device_alloc(size_t bytes);          /* hipMalloc; NULL on failure */
 void  selenite_rx_device_free(void *dptr);

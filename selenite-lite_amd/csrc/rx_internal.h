@@ -282,6 +282,42 @@ struct __attribute__((visibility("hidden"))) IqcStage {
     int run(selenite_rx_instance *S, ChanRange r, const void *src, bool src_q15, uint32_t block_size, const void **corrected_src);
 };
 
+// ---- signal-level meter and squelch (rx_meter.hip): arm_power_f32 per DSP block of the un-scaled audio -> level -> open / close, in front
+// of the AGC; the gate zeroes the closed blocks behind it ----
+struct MeterParams {
+    uint32_t channels;     // channels of this launch (a ChanRange: the five state rows and `bits` are offset to it)
+    uint32_t n;            // audio samples of a DSP block: block / decim
+    uint32_t nblk;         // DSP blocks per channel in this launch
+    uint32_t stride;       // audio samples between consecutive channels (RxParams::out_stride)
+    uint32_t sense;        // SELENITE_RX_SQ_*
+    uint32_t hang;
+    float attack, decay, open_level, close_level;
+    float *level;          // [C]
+    uint32_t *open;        // [C] 0 / 1
+    uint32_t *hold;        // [C]
+    uint64_t *opens;       // [C] closed -> open transitions so far
+    uint64_t *open_blocks; // [C] blocks that ended open so far
+    uint8_t *bits;         // [C][nblk] the gate of every block of this launch: `open` behind its update (k_meter writes, k_gate reads)
+};
+hipError_t launch_meter(const MeterParams &q, const float *audio, hipStream_t st);
+// zeros over the blocks of dst (f32 or int16, rows `stride` apart) whose byte in q.bits is 0
+hipError_t launch_gate(const MeterParams &q, void *dst, bool dst_q15, hipStream_t st);
+// the stage's part of the instance (selenite_rx_set_meter): on = false: no stage, no buffers
+struct __attribute__((visibility("hidden"))) MeterStage {
+    bool on = false;
+    uint32_t sense = 0, gate = 0, hang = 0;
+    float attack = 0.0f, decay = 0.0f, open_level = 0.0f, close_level = 0.0f, level_init = 0.0f;
+    float *d_level = nullptr;                               // [channels]
+    uint32_t *d_open = nullptr, *d_hold = nullptr;          // [channels] each
+    uint64_t *d_opens = nullptr, *d_open_blocks = nullptr;  // [channels] each
+    // the gate bytes of the last launch, [cfg.channels][blocks of the launch], indexed by absolute channel; grown by the first call that needs
+    // it; lives from selenite_rx_global_phase1_device to _phase2_device
+    uint8_t *d_bits = nullptr; size_t bits_bytes = 0;
+    void release();                                         // frees the buffers: no stage
+    int init_state(selenite_rx_instance *S);                // the state set_meter leaves
+    MeterParams params(ChanRange r, const RxParams &p) const;   // the stage's view of a launch: the channels and the audio geometry of `p`
+};
+
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
     SelPlan sel;                  // what select() reads: the shape (kind 0 = none), dense or not, which operands exist (rx_select.h)
@@ -376,6 +412,7 @@ struct selenite_rx_instance {
     int no_periodic_lo = 0;            // SELENITE_RX_NO_PERIODIC_LO=1: never keep a periodic shared LO in registers
     int force_generic = 0;             // SELENITE_RX_FORCE_GENERIC=1 (tests cross-check both paths)
     srx::NrStage nr;                   // NLMS noise reduction / automatic notch, in front of the AGC (rx_nlms.hip)
+    srx::MeterStage meter;             // signal-level meter and squelch, between NLMS and the AGC; its gate behind the AGC (rx_meter.hip)
     srx::OutStage out;                 // audio output stage, behind the chain (rx_out.hip)
     srx::SpecStage spec;               // spectrum tap, in front of the chain (rx_spectrum.hip)
     srx::IqcStage iqc;                 // I/Q correction, between the spectrum tap and the noise blanker (rx_iqc.hip)

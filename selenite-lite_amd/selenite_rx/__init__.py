@@ -24,6 +24,7 @@ SUCCESS, ARGUMENT_ERROR, LENGTH_ERROR, NANINF, DEVICE_ERROR = 0, -1, -2, -4, -7
 NR_OFF, NR_DENOISE, NR_NOTCH = 0, 1, 2                         # selenite_rx_set_nr: the NLMS stage's kind
 OUT_MONO, OUT_STEREO = 0, 1                                    # selenite_rx_set_out: the output stage's frame format
 WINDOW_HANN, WINDOW_BLACKMAN_HARRIS = 0, 1                     # selenite_rx_design_window
+SQ_ABOVE, SQ_BELOW = 0, 1                                      # selenite_rx_set_meter: the squelch's sense
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -105,6 +106,17 @@ class IqcStateView(C.Structure):
     _fields_ = [("dc_i", f32p), ("dc_q", f32p), ("p", f32p), ("g", f32p), ("held", u64p)]
 
 
+class MeterConfig(C.Structure):
+    """struct selenite_rx_meter_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("sense", C.c_uint32), ("gate", C.c_uint32), ("hang", C.c_uint32), ("attack", C.c_float),
+                ("decay", C.c_float), ("open_level", C.c_float), ("close_level", C.c_float), ("level_init", C.c_float)]
+
+
+class MeterStateView(C.Structure):
+    """struct selenite_rx_meter_state_view."""
+    _fields_ = [("level", f32p), ("open", u32p), ("hold", u32p), ("opens", u64p), ("open_blocks", u64p)]
+
+
 # every symbol include/selenite_rx.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "selenite_rx_init", "selenite_rx_free", "selenite_rx_set_mode", "selenite_rx_status",
@@ -128,6 +140,8 @@ ABI_SYMBOLS = [
     "selenite_rx_set_spectrum_state", "selenite_rx_spectrum_twiddles", "selenite_rx_design_window",
     "selenite_rx_set_nb", "selenite_rx_get_nb_state", "selenite_rx_set_nb_state",
     "selenite_rx_set_iqc", "selenite_rx_get_iqc_state", "selenite_rx_set_iqc_state",
+    "selenite_rx_set_meter", "selenite_rx_get_meter_state", "selenite_rx_set_meter_state", "selenite_rx_meter_level_device",
+    "selenite_rx_meter_open_device",
 ]
 
 class TxConfig(C.Structure):
@@ -272,6 +286,14 @@ def lib():
             L.selenite_rx_set_iqc.argtypes = [vp, C.POINTER(IqcConfig)]
             L.selenite_rx_get_iqc_state.argtypes = [vp, C.POINTER(IqcStateView)]
             L.selenite_rx_set_iqc_state.argtypes = [vp, C.POINTER(IqcStateView)]
+        if hasattr(L, "selenite_rx_set_meter"):             # (an older build named by SELENITE_RX_LIB lacks the level meter)
+            L.selenite_rx_set_meter.argtypes = [vp, C.POINTER(MeterConfig)]
+            L.selenite_rx_get_meter_state.argtypes = [vp, C.POINTER(MeterStateView)]
+            L.selenite_rx_set_meter_state.argtypes = [vp, C.POINTER(MeterStateView)]
+            L.selenite_rx_meter_level_device.argtypes = [vp]
+            L.selenite_rx_meter_level_device.restype = vp
+            L.selenite_rx_meter_open_device.argtypes = [vp]
+            L.selenite_rx_meter_open_device.restype = vp
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -891,6 +913,58 @@ class Rx:
         rc = self.L.selenite_rx_set_iqc_state(self.h, C.byref(v))
         if rc:
             raise RxError(rc, "selenite_rx_set_iqc_state")
+
+    # -- signal-level meter and squelch (selenite_rx_set_meter) -----------------------------------
+    METER_TYPES = dict(level=np.float32, open=np.uint32, hold=np.uint32, opens=np.uint64, open_blocks=np.uint64)
+    METER_PTRS = dict(level=f32p, open=u32p, hold=u32p, opens=u64p, open_blocks=u64p)
+
+    def set_meter(self, sense=SQ_ABOVE, gate=1, hang=0, attack=0.5, decay=0.125, open_level=1e-6, close_level=5e-7, level_init=0.0):
+        """Put the level meter / squelch on the un-scaled audio of every channel, in front of the AGC (gate=1: closed DSP blocks leave as
+        zeros, behind the AGC), or remove it (sense=None).  Sets the stage's state to level_init, closed, counters zero.  Raises RxError on
+        a bad field; the instance is then left as it was."""
+        old, self._meter = getattr(self, "_meter", None), None
+        if sense is None:
+            rc = self.L.selenite_rx_set_meter(self.h, None)
+        else:
+            g = MeterConfig()
+            g.struct_size, g.sense, g.gate, g.hang = C.sizeof(MeterConfig), int(sense), int(gate), int(hang)
+            g.attack, g.decay, g.open_level, g.close_level, g.level_init = float(attack), float(decay), float(open_level), float(close_level), float(level_init)
+            rc = self.L.selenite_rx_set_meter(self.h, C.byref(g))
+        if rc == ARGUMENT_ERROR:
+            self._meter = old
+        if rc:
+            raise RxError(rc, self.L.selenite_rx_error_string(None).decode() if rc == ARGUMENT_ERROR else self.error())
+        self._meter = True if sense is not None else None
+
+    def meter_state(self):
+        """dict(level f32, open u32, hold u32, opens u64, open_blocks u64, each [channels]); drains the stream"""
+        if getattr(self, "_meter", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the level meter is off")
+        a = {k: np.zeros(self.cfg.channels, t) for k, t in self.METER_TYPES.items()}
+        v = MeterStateView(*[a[k].ctypes.data_as(self.METER_PTRS[k]) for k in self.METER_TYPES])
+        rc = self.L.selenite_rx_get_meter_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_meter_state")
+        return a
+
+    def set_meter_state(self, d):
+        if getattr(self, "_meter", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the level meter is off")
+        a = {k: np.ascontiguousarray(d[k], self.METER_TYPES[k]) for k in d}
+        for k in a:
+            assert a[k].shape == (self.cfg.channels,), (k, a[k].shape)
+        v = MeterStateView(*[a[k].ctypes.data_as(self.METER_PTRS[k]) if k in a else None for k in self.METER_TYPES])
+        rc = self.L.selenite_rx_set_meter_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_set_meter_state")
+
+    def meter_level_device(self):
+        """device address of the level row (None while the stage is off)"""
+        return self.L.selenite_rx_meter_level_device(self.h)
+
+    def meter_open_device(self):
+        """device address of the open row (None while the stage is off)"""
+        return self.L.selenite_rx_meter_open_device(self.h)
 
     def close(self):
         if self.h:
