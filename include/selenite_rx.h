@@ -28,6 +28,7 @@
  *   -> arm_fir_f32 (delay taps) on I, arm_fir_f32 (Hilbert taps) on Q
  *   -> arm_sub_f32 / arm_add_f32 (USB / LSB)   [AM: arm_cmplx_mag_f32]
  *   -> arm_biquad_cascade_df1_f32 (CW narrow filter)
+ *   -> [optional: arm_biquad_cascade_df1_f32 audio filter (notch, de-emphasis, EQ), selenite_rx_set_afilt]
  *   -> [optional: arm_lms_norm_f32 noise reduction / automatic notch, selenite_rx_set_nr]
  *   -> [optional: arm_power_f32 per DSP block -> level meter -> squelch decision, selenite_rx_set_meter]
  *   -> arm_abs_f32 + arm_max_f32 -> gain law -> arm_scale_f32 (AGC)
@@ -394,6 +395,36 @@ typedef struct selenite_rx_meter_state_view {
     uint64_t *open_blocks;    /* DSP blocks that ended open since set_meter / reset */
 } selenite_rx_meter_state_view;
 
+/* ---- audio biquad filter (on the un-scaled audio behind the demodulator and the CW filter, in
+ * front of NLMS, the level meter and the AGC; off by default) ----------------------------------------------------------------------------
+ * A manual notch, FM de-emphasis, tone control, an audio high-pass or low-pass: NLMS adapts on the filtered audio and the meter sees what
+ * the listener hears.  Every mode, every arith mode.  The un-scaled audio of a channel is one stream, a call contributes
+ * nout = blockSize / decim samples; per channel
+ *   arm_biquad_cascade_df1_f32(S, x, x, nout)     FilteringFunctions/arm_biquad_cascade_df1_f32.c:165-407, in place, stage-outer
+ *     per stage s = 0 .. n_stages-1, coefficients {b0, b1, b2, a1, a2} (CMSIS sign: the a's are ADDED), state {x1, x2, y1, y2}:
+ *     acc = b0 * x[n];  acc = acc + b1 * x1;  acc = acc + b2 * x2;  acc = acc + a1 * y1;  acc = acc + a2 * y2
+ *     x2 = x1; x1 = x[n]; y2 = y1; y1 = acc; x[n] = acc
+ * every product rounded to f32, then every sum; no contraction, denormals kept, in SELENITE_ARITH_CMSIS, _FMA, _SPLIT16 and _AUTO alike:
+ * bit-exact given its input, and the bits do not depend on how the stream is cut into calls.  Coefficients are one set [n_stages][5] for
+ * all channels, or with per_channel = 1 one set per channel, [channels][n_stages][5] (a notch where each channel's heterodyne is); they
+ * must be finite and are copied.  Stability is the caller's business: the stage neither raises nor clears SELENITE_RX_NANINF, and a state
+ * that became NaN stays NaN until selenite_rx_reset or selenite_rx_set_afilt_state, as with CMSIS.  State: [channels][n_stages][4] in
+ * CMSIS pState order, +0.0f after set_afilt and reset. */
+#define SELENITE_RX_AFILT_MAX_STAGES 8
+typedef struct selenite_rx_afilt_config {
+    uint32_t struct_size;     /* = sizeof(selenite_rx_afilt_config) (this struct's own growth path) */
+    uint32_t n_stages;        /* 1 .. 8 */
+    uint32_t per_channel;     /* 0: coeffs [n_stages][5]; 1: coeffs [channels][n_stages][5] */
+    uint32_t reserved;        /* 0 */
+    const float *coeffs;      /* finite, copied */
+} selenite_rx_afilt_config;
+
+/* The stage's state and, for get only, its coefficients as configured.  NULL members are skipped. */
+typedef struct selenite_rx_afilt_state_view {
+    float *state;             /* [channels][n_stages][4] {x1, x2, y1, y2} */
+    float *coeffs;            /* [n_stages][5] or [channels][n_stages][5], as configured; get only */
+} selenite_rx_afilt_state_view;
+
 typedef struct selenite_rx_instance selenite_rx_instance;  /* opaque; state lives in HBM */
 
 /* ---- instance life cycle ------------------------------------------------------------- */
@@ -619,6 +650,29 @@ int selenite_rx_set_meter_state(selenite_rx_instance *S, const selenite_rx_meter
 const float *selenite_rx_meter_level_device(const selenite_rx_instance *S);
 const uint32_t *selenite_rx_meter_open_device(const selenite_rx_instance *S);
 
+/* ---- audio biquad filter ------------------------------------------------------------------ */
+
+/* Sets the filter for every channel (selenite_rx_afilt_config), or removes it and releases its buffers (f == NULL).  Clears the stage's
+ * state to +0.0f and touches nothing else.  A bad field (SELENITE_RX_ARGUMENT_ERROR: n_stages out of range, per_channel not 0 / 1, NULL
+ * or non-finite coeffs, a wrong struct_size, reserved != 0) leaves the instance as it was, a working stage included.
+ * SELENITE_RX_DEVICE_ERROR is different: the old stage is released before the new rows are allocated, so a failed allocation leaves the
+ * instance with NO stage (as after f == NULL), its chain untouched.  selenite_rx_set_mode, _set_nr, _set_meter, _set_out, _set_spectrum,
+ * _set_nb and _set_iqc leave it alone; selenite_rx_reset clears the state and keeps the coefficients.  Every process entry point runs it
+ * once per call (f32 and int16 slots, device and host pointers, the timing calls, global phase 1, selenite_rx_global_process_f32_device
+ * -- not phase 2).  With the stage on, the fused kernels run with their own AGC off and the generic AGC kernel finishes the call, as with
+ * NLMS.  With the stage off no launch, byte, allocation or output of any call changes. */
+int selenite_rx_set_afilt(selenite_rx_instance *S, const selenite_rx_afilt_config *f);
+/* Replaces the coefficient rows of channels first_channel .. first_channel + n_channels - 1 (coeffs [n_channels][n_stages][5], finite)
+ * and leaves the state alone: a notch is retuned while the user listens, without the click of a cleared delay line.  Ordered on the
+ * instance's stream: calls issued before it run with the old rows, calls issued after it with the new ones; the caller may free coeffs
+ * on return.  per_channel == 0: the only valid range is (0, 1).  SELENITE_RX_ARGUMENT_ERROR (stage off, range out of bounds, NULL or
+ * non-finite coeffs) leaves the stage as it was. */
+int selenite_rx_set_afilt_coeffs(selenite_rx_instance *S, uint32_t first_channel, uint32_t n_channels, const float *coeffs);
+/* Host copies of the state (and, get only, the coefficients).  Drains the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the stage
+ * is off. */
+int selenite_rx_get_afilt_state(selenite_rx_instance *S, const selenite_rx_afilt_state_view *dst);
+int selenite_rx_set_afilt_state(selenite_rx_instance *S, const selenite_rx_afilt_state_view *src);
+
 void *selenite_rx_device_alloc(size_t bytes);          /* hipMalloc; NULL on failure */
 void  selenite_rx_device_free(void *dptr);
 int   selenite_rx_memcpy_h2d(void *dptr, const void *hptr, size_t bytes);
@@ -721,6 +775,18 @@ int selenite_rx_design_interp(float *coeffs, uint32_t ni_taps, uint32_t interp, 
 /* A window for the spectrum tap, periodic form over n points (n >= 2): SELENITE_RX_WINDOW_HANN 0.5 - 0.5 cos(2 pi i / n), or
  * SELENITE_RX_WINDOW_BLACKMAN_HARRIS (four terms, -92 dB side lobes). */
 int selenite_rx_design_window(float *w, uint32_t n, int kind);
+
+/* One RBJ cookbook section for the audio filter stage, in CMSIS order and sign {b0, b1, b2, -a1, -a2} / a0: w = 2 pi f0 (0 < f0 < 0.5
+ * cycles per sample), alpha = sin w / (2 q) (q > 0), A = 10^(gain_db / 40) (SELENITE_RX_BIQUAD_PEAKING only; finite).  Computed in double,
+ * rounded once. */
+#define SELENITE_RX_BIQUAD_NOTCH    0
+#define SELENITE_RX_BIQUAD_PEAKING  1
+#define SELENITE_RX_BIQUAD_LOWPASS  2
+#define SELENITE_RX_BIQUAD_HIGHPASS 3
+int selenite_rx_design_biquad(float coeffs[5], int kind, double f0, double q, double gain_db);
+/* FM de-emphasis, one pole: p = exp(-1 / tau_samples) (tau_samples > 0: the time constant in samples of the audio rate, 75 us at 12 kHz
+ * is 0.9), {1 - p, 0, 0, p, 0}: unity gain at DC. */
+int selenite_rx_design_deemphasis(float coeffs[5], double tau_samples);
 
 int selenite_rx_abi_version(void);
 

@@ -85,3 +85,51 @@ extern "C" int selenite_rx_design_window(float *w, uint32_t n, int kind)
     }
     return SELENITE_RX_SUCCESS;
 }
+
+extern "C" int selenite_rx_design_biquad(float coeffs[5], int kind, double f0, double q, double gain_db)
+{
+    if (!coeffs || !(f0 > 0.0 && f0 < 0.5) || !(q > 0.0) || !std::isfinite(q)) return SELENITE_RX_ARGUMENT_ERROR;
+    const double w0 = 2.0 * kPi * f0, cw = std::cos(w0), alpha = std::sin(w0) / (2.0 * q);
+    double b0, b1, b2, a0, a1, a2;
+    switch (kind) {
+    case SELENITE_RX_BIQUAD_NOTCH:
+        b0 = 1.0; b1 = -2.0 * cw; b2 = 1.0;
+        a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha;
+        break;
+    case SELENITE_RX_BIQUAD_PEAKING: {
+        if (!std::isfinite(gain_db)) return SELENITE_RX_ARGUMENT_ERROR;
+        const double A = std::pow(10.0, gain_db / 40.0);
+        b0 = 1.0 + alpha * A; b1 = -2.0 * cw; b2 = 1.0 - alpha * A;
+        a0 = 1.0 + alpha / A; a1 = -2.0 * cw; a2 = 1.0 - alpha / A;
+        break;
+    }
+    case SELENITE_RX_BIQUAD_LOWPASS:
+        b0 = (1.0 - cw) / 2.0; b1 = 1.0 - cw; b2 = (1.0 - cw) / 2.0;
+        a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha;
+        break;
+    case SELENITE_RX_BIQUAD_HIGHPASS:
+        b0 = (1.0 + cw) / 2.0; b1 = -(1.0 + cw); b2 = (1.0 + cw) / 2.0;
+        a0 = 1.0 + alpha; a1 = -2.0 * cw; a2 = 1.0 - alpha;
+        break;
+    default:
+        return SELENITE_RX_ARGUMENT_ERROR;
+    }
+    coeffs[0] = (float)(b0 / a0);
+    coeffs[1] = (float)(b1 / a0);
+    coeffs[2] = (float)(b2 / a0);
+    coeffs[3] = (float)(-a1 / a0);
+    coeffs[4] = (float)(-a2 / a0);
+    return SELENITE_RX_SUCCESS;
+}
+
+extern "C" int selenite_rx_design_deemphasis(float coeffs[5], double tau_samples)
+{
+    if (!coeffs || !(tau_samples > 0.0) || !std::isfinite(tau_samples)) return SELENITE_RX_ARGUMENT_ERROR;
+    const double p = std::exp(-1.0 / tau_samples);
+    coeffs[0] = (float)(1.0 - p);
+    coeffs[1] = 0.0f;
+    coeffs[2] = 0.0f;
+    coeffs[3] = (float)p;
+    coeffs[4] = 0.0f;
+    return SELENITE_RX_SUCCESS;
+}

@@ -318,6 +318,29 @@ struct __attribute__((visibility("hidden"))) MeterStage {
     MeterParams params(ChanRange r, const RxParams &p) const;   // the stage's view of a launch: the channels and the audio geometry of `p`
 };
 
+// ---- audio biquad filter (rx_afilt.hip): arm_biquad_cascade_df1_f32 in place on the un-scaled audio, behind the demodulator and the CW
+// filter, in front of NLMS, the meter and the AGC ----
+struct AfiltParams {
+    uint32_t channels;     // channels of this launch (a ChanRange: `state` and per-channel `coeffs` are offset to it)
+    uint32_t nout;         // audio samples per channel in this call
+    uint32_t stride;       // audio samples between consecutive channels (RxParams::out_stride)
+    uint32_t n_stages;     // 1 .. 8
+    uint32_t per_channel;  // 0: coeffs [n_stages][5]; 1: coeffs [C][n_stages][5]
+    const float *coeffs;
+    float *state;          // [C][n_stages][4] { x1, x2, y1, y2 }
+};
+hipError_t launch_afilt(const AfiltParams &q, float *audio, hipStream_t st);
+// the stage's part of the instance (selenite_rx_set_afilt): on = false: no stage, no buffers
+struct __attribute__((visibility("hidden"))) AfiltStage {
+    bool on = false;
+    uint32_t n_stages = 0, per_channel = 0;
+    float *d_coeffs = nullptr;                              // [n_stages][5] | [channels][n_stages][5]
+    float *d_state = nullptr;                               // [channels][n_stages][4]
+    void release();                                         // frees the buffers: no stage
+    int init_state(selenite_rx_instance *S);                // the state set_afilt leaves: +0.0f
+    AfiltParams params(ChanRange r, const RxParams &p) const;   // the stage's view of a launch: the channels and the audio geometry of `p`
+};
+
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
     SelPlan sel;                  // what select() reads: the shape (kind 0 = none), dense or not, which operands exist (rx_select.h)
@@ -411,6 +434,7 @@ struct selenite_rx_instance {
     int no_shared_lo = 0;              // SELENITE_RX_NO_SHARED_LO=1: always compute the LO per channel
     int no_periodic_lo = 0;            // SELENITE_RX_NO_PERIODIC_LO=1: never keep a periodic shared LO in registers
     int force_generic = 0;             // SELENITE_RX_FORCE_GENERIC=1 (tests cross-check both paths)
+    srx::AfiltStage afilt;             // audio biquad filter, behind the demodulator / CW filter, in front of NLMS (rx_afilt.hip)
     srx::NrStage nr;                   // NLMS noise reduction / automatic notch, in front of the AGC (rx_nlms.hip)
     srx::MeterStage meter;             // signal-level meter and squelch, between NLMS and the AGC; its gate behind the AGC (rx_meter.hip)
     srx::OutStage out;                 // audio output stage, behind the chain (rx_out.hip)

@@ -117,6 +117,18 @@ class MeterStateView(C.Structure):
     _fields_ = [("level", f32p), ("open", u32p), ("hold", u32p), ("opens", u64p), ("open_blocks", u64p)]
 
 
+class AfiltConfig(C.Structure):
+    """struct selenite_rx_afilt_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_stages", C.c_uint32), ("per_channel", C.c_uint32), ("reserved", C.c_uint32), ("coeffs", f32p)]
+
+
+class AfiltStateView(C.Structure):
+    """struct selenite_rx_afilt_state_view."""
+    _fields_ = [("state", f32p), ("coeffs", f32p)]
+
+
+BIQUAD_NOTCH, BIQUAD_PEAKING, BIQUAD_LOWPASS, BIQUAD_HIGHPASS = 0, 1, 2, 3      # selenite_rx_design_biquad: kind
+
 # every symbol include/selenite_rx.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "selenite_rx_init", "selenite_rx_free", "selenite_rx_set_mode", "selenite_rx_status",
@@ -142,6 +154,8 @@ ABI_SYMBOLS = [
     "selenite_rx_set_iqc", "selenite_rx_get_iqc_state", "selenite_rx_set_iqc_state",
     "selenite_rx_set_meter", "selenite_rx_get_meter_state", "selenite_rx_set_meter_state", "selenite_rx_meter_level_device",
     "selenite_rx_meter_open_device",
+    "selenite_rx_set_afilt", "selenite_rx_set_afilt_coeffs", "selenite_rx_get_afilt_state", "selenite_rx_set_afilt_state",
+    "selenite_rx_design_biquad", "selenite_rx_design_deemphasis",
 ]
 
 class TxConfig(C.Structure):
@@ -294,6 +308,13 @@ def lib():
             L.selenite_rx_meter_level_device.restype = vp
             L.selenite_rx_meter_open_device.argtypes = [vp]
             L.selenite_rx_meter_open_device.restype = vp
+        if hasattr(L, "selenite_rx_set_afilt"):             # (an older build named by SELENITE_RX_LIB lacks the audio filter)
+            L.selenite_rx_set_afilt.argtypes = [vp, C.POINTER(AfiltConfig)]
+            L.selenite_rx_set_afilt_coeffs.argtypes = [vp, C.c_uint32, C.c_uint32, f32p]
+            L.selenite_rx_get_afilt_state.argtypes = [vp, C.POINTER(AfiltStateView)]
+            L.selenite_rx_set_afilt_state.argtypes = [vp, C.POINTER(AfiltStateView)]
+            L.selenite_rx_design_biquad.argtypes = [f32p, C.c_int, C.c_double, C.c_double, C.c_double]
+            L.selenite_rx_design_deemphasis.argtypes = [f32p, C.c_double]
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -317,6 +338,24 @@ def design_lowpass(num_taps, cutoff):
     if rc:
         raise ValueError("selenite_rx_design_lowpass: %d" % rc)
     return h
+
+
+def design_biquad(kind, f0, q, gain_db=0.0):
+    """one RBJ section for Rx.set_afilt, CMSIS order and sign {b0, b1, b2, -a1, -a2} / a0; f0 in cycles per sample of the audio rate"""
+    c = np.empty(5, np.float32)
+    rc = lib().selenite_rx_design_biquad(_fp(c), int(kind), float(f0), float(q), float(gain_db))
+    if rc:
+        raise ValueError("selenite_rx_design_biquad: %d" % rc)
+    return c
+
+
+def design_deemphasis(tau_samples):
+    """one-pole FM de-emphasis for Rx.set_afilt: p = exp(-1 / tau_samples), {1 - p, 0, 0, p, 0}"""
+    c = np.empty(5, np.float32)
+    rc = lib().selenite_rx_design_deemphasis(_fp(c), float(tau_samples))
+    if rc:
+        raise ValueError("selenite_rx_design_deemphasis: %d" % rc)
+    return c
 
 
 def design_interp(ni_taps, interp, cutoff):
@@ -965,6 +1004,65 @@ class Rx:
     def meter_open_device(self):
         """device address of the open row (None while the stage is off)"""
         return self.L.selenite_rx_meter_open_device(self.h)
+
+    # -- audio biquad filter (selenite_rx_set_afilt) -----------------------------------------------
+    def set_afilt(self, coeffs, per_channel=False):
+        """Put a biquad cascade (arm_biquad_cascade_df1_f32) on the un-scaled audio of every channel, in front of NLMS, the meter and the
+        AGC, or remove it (coeffs=None).  coeffs: [n_stages][5] for all channels, or with per_channel [channels][n_stages][5]; CMSIS order
+        and sign.  Clears the stage's state.  Raises RxError on a bad field; the instance is then left as it was."""
+        old, self._afilt = getattr(self, "_afilt", None), None
+        if coeffs is None:
+            rc, new = self.L.selenite_rx_set_afilt(self.h, None), None
+        else:
+            a = np.ascontiguousarray(coeffs, np.float32)
+            want = 3 if per_channel else 2
+            if a.ndim == 1 and not per_channel and a.size == 5:
+                a = a.reshape(1, 5)
+            if a.ndim != want or a.shape[-1] != 5 or (per_channel and a.shape[0] != self.cfg.channels):
+                self._afilt = old
+                raise RxError(ARGUMENT_ERROR, "set_afilt: coeffs is not [n_stages][5] / [channels][n_stages][5]")
+            g = AfiltConfig()
+            g.struct_size, g.n_stages, g.per_channel, g.reserved, g.coeffs = C.sizeof(AfiltConfig), a.shape[-2], int(bool(per_channel)), 0, _fp(a)
+            rc, new = self.L.selenite_rx_set_afilt(self.h, C.byref(g)), (int(a.shape[-2]), bool(per_channel))
+        if rc == ARGUMENT_ERROR:
+            self._afilt = old
+        if rc:
+            raise RxError(rc, self.L.selenite_rx_error_string(None).decode() if rc == ARGUMENT_ERROR else self.error())
+        self._afilt = new
+
+    def set_afilt_coeffs(self, coeffs, first_channel=0):
+        """Replace the coefficient rows of channels first_channel .. (coeffs [n][n_stages][5]; one shared set: [n_stages][5]) and keep the
+        state; ordered on the instance's stream."""
+        a = np.ascontiguousarray(coeffs, np.float32)
+        n = a.shape[0] if a.ndim == 3 else 1
+        rc = self.L.selenite_rx_set_afilt_coeffs(self.h, int(first_channel), int(n), _fp(a))
+        if rc:
+            raise RxError(rc, self.L.selenite_rx_error_string(None).decode() if rc == ARGUMENT_ERROR else self.error())
+
+    def _afilt_shapes(self):
+        if getattr(self, "_afilt", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the audio filter is off")
+        ns, per = self._afilt
+        return (self.cfg.channels, ns, 4), ((self.cfg.channels, ns, 5) if per else (ns, 5))
+
+    def afilt_state(self):
+        """dict(state f32 [channels][n_stages][4] {x1, x2, y1, y2}, coeffs f32 as configured); drains the stream"""
+        ss, cs = self._afilt_shapes()
+        a = dict(state=np.zeros(ss, np.float32), coeffs=np.zeros(cs, np.float32))
+        v = AfiltStateView(_fp(a["state"]), _fp(a["coeffs"]))
+        rc = self.L.selenite_rx_get_afilt_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_afilt_state")
+        return a
+
+    def set_afilt_state(self, state):
+        ss, _ = self._afilt_shapes()
+        a = np.ascontiguousarray(state["state"] if isinstance(state, dict) else state, np.float32)
+        assert a.shape == ss, (a.shape, ss)
+        v = AfiltStateView(_fp(a), None)
+        rc = self.L.selenite_rx_set_afilt_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_set_afilt_state")
 
     def close(self):
         if self.h:
