@@ -28,6 +28,7 @@
  *   -> arm_fir_f32 (delay taps) on I, arm_fir_f32 (Hilbert taps) on Q
  *   -> arm_sub_f32 / arm_add_f32 (USB / LSB)   [AM: arm_cmplx_mag_f32]
  *   -> arm_biquad_cascade_df1_f32 (CW narrow filter)
+ *   -> [optional tap: Goertzel tone-detector bank (CTCSS, DTMF, selcall), selenite_rx_set_tones]
  *   -> [optional: arm_biquad_cascade_df1_f32 audio filter (notch, de-emphasis, EQ), selenite_rx_set_afilt]
  *   -> [optional: arm_lms_norm_f32 noise reduction / automatic notch, selenite_rx_set_nr]
  *   -> [optional: arm_power_f32 per DSP block -> level meter -> squelch decision, selenite_rx_set_meter]
@@ -425,6 +426,63 @@ typedef struct selenite_rx_afilt_state_view {
     float *coeffs;            /* [n_stages][5] or [channels][n_stages][5], as configured; get only */
 } selenite_rx_afilt_state_view;
 
+/* ---- tone-detector bank (a TAP on the un-scaled audio behind the demodulator and the CW
+ * filter, in front of the audio filter, NLMS, the level meter and the AGC; off by default) -----------------------------------------------
+ * Which of K known tones is in the channel: CTCSS tone squelch, DTMF, selective calling, a 1750 Hz burst, a CW pitch indicator.  The
+ * stage reads the audio and changes none of it (a CTCSS tone is seen in front of the high-pass that removes it).  Every mode, every arith
+ * mode.  The un-scaled audio of a channel is one stream; n = block / decim; a frame is frame_blocks consecutive DSP blocks of it,
+ * N = frame_blocks * n samples, counted from selenite_rx_set_tones / selenite_rx_reset, not per call: one `position` (uint64, in DSP
+ * blocks) says where the stream stands, a frame may straddle calls and a call may end several frames.  One table of K tones for all
+ * channels, three floats each: {c, cw, sw} = {2 cos w, cos w, sin w}, w = 2 pi f, 0 < f < 0.5 cycles per audio sample
+ * (selenite_rx_design_tones); finite, copied.  Every operation below is rounded to f32; no contraction, denormals kept.
+ *   per sample x and tone k, state s1, s2 (+0.0f at a frame's start):
+ *     t = c * s1;  s0 = x + t;  s0 = s0 - s2;  s2 = s1;  s1 = s0
+ *   per sample, once per channel (arm_power_f32's sum, +0.0f at a frame's start):
+ *     e = x * x;  E = E + e
+ *   at the frame's last sample, per tone (arm_cmplx_mag_squared_f32's form):
+ *     u = cw * s2;  re = s1 - u;  im = sw * s2;  a = re * re;  b = im * im;  p[k] = a + b
+ *   then per channel (arm_max_f32, StatisticsFunctions/arm_max_f32.c: the first index of the maximum; a NaN wins only at index 0):
+ *     (p_best, best) = arm_max_f32(p, K)
+ *     t = ratio * E;  t = t * (float)N
+ *     hit = p_best > t && p_best > min_power && p_best <= FLT_MAX
+ *     w = hit ? best : SELENITE_RX_TONE_NONE
+ *     if (w == cand) run = min(run + 1, 65535); else { cand = w; run = 1; }
+ *     if (cand != tone && run >= (cand == NONE ? release : confirm)) { tone = cand; changes += 1; }
+ *     power[k] = p[k];  frame_energy = E;  last_best = best           (the rows a reader sees)
+ *     s1 = s2 = +0.0f for every tone;  E = +0.0f
+ * The recurrence is arm_biquad_cascade_df1_f32 with the one section {1, 0, 0, c, -1} (s1 = y1, s2 = y2) less its two dead products
+ * 0 * x1 and 0 * x2: the same bits on finite input that holds no -0.0f.  The three-operation form is the specification: a -0.0f sample can
+ * give a zero of the other sign (c < 0, zero state, x = -0.0f: -0.0f here, +0.0f there) and an Inf sample becomes NaN one step later here.
+ * The stage neither raises nor clears SELENITE_RX_NANINF; a non-finite sample poisons its own frame only (the state is cleared at the
+ * frame's end).  State after set_tones and reset: s, E, power, frame_energy +0.0f; last_best, run, changes, position 0; tone, cand NONE. */
+#define SELENITE_RX_TONES_MAX  64
+#define SELENITE_RX_TONE_NONE  0xFFFFFFFFu
+typedef struct selenite_rx_tones_config {
+    uint32_t struct_size;    /* = sizeof(selenite_rx_tones_config) (this struct's own growth path) */
+    uint32_t n_tones;        /* K: 1 .. 64 */
+    uint32_t frame_blocks;   /* 1 .. 65535 DSP blocks per frame (frame_blocks * block / decim < 2^31) */
+    uint32_t confirm;        /* 1 .. 65535 consecutive frames before a tone is reported */
+    uint32_t release;        /* 1 .. 65535 consecutive frames without a hit before NONE is reported */
+    uint32_t reserved;       /* 0 */
+    float ratio;             /* finite, 0 <= ratio <= 1: p_best against E * N (a pure tone alone gives 0.5) */
+    float min_power;         /* finite, >= 0 */
+    const float *coeffs;     /* [n_tones][3] {2 cos w, cos w, sin w}, finite, copied */
+} selenite_rx_tones_config;
+
+/* The stage's state.  NULL members are skipped. */
+typedef struct selenite_rx_tones_state_view {
+    float *s;                 /* [channels][n_tones][2] {s1, s2} of the running frame */
+    float *energy;            /* [channels] E of the running frame */
+    float *power;             /* [channels][n_tones] p of the last whole frame */
+    float *frame_energy;      /* [channels] E of the last whole frame */
+    uint32_t *last_best;      /* [channels] best of the last whole frame */
+    uint32_t *tone;           /* [channels] the reported tone, or SELENITE_RX_TONE_NONE */
+    uint32_t *cand;           /* [channels] the candidate */
+    uint32_t *run;            /* [channels] consecutive frames of the candidate, saturating at 65535 */
+    uint64_t *changes;        /* [channels] changes of `tone` since set_tones / reset */
+    uint64_t *position;       /* ONE value: DSP blocks per channel since set_tones / reset */
+} selenite_rx_tones_state_view;
+
 typedef struct selenite_rx_instance selenite_rx_instance;  /* opaque; state lives in HBM */
 
 /* ---- instance life cycle ------------------------------------------------------------- */
@@ -673,6 +731,30 @@ int selenite_rx_set_afilt_coeffs(selenite_rx_instance *S, uint32_t first_channel
 int selenite_rx_get_afilt_state(selenite_rx_instance *S, const selenite_rx_afilt_state_view *dst);
 int selenite_rx_set_afilt_state(selenite_rx_instance *S, const selenite_rx_afilt_state_view *src);
 
+/* ---- tone-detector bank ----------------------------------------------------------------------- */
+
+/* Sets the bank for every channel (selenite_rx_tones_config), or removes it and releases its buffers (f == NULL).  Puts the stage's state
+ * at its start and touches nothing else.  A bad field (SELENITE_RX_ARGUMENT_ERROR: n_tones, frame_blocks, confirm or release out of range,
+ * a frame of 2^31 samples or more, ratio outside [0, 1], min_power negative, either not finite, NULL or non-finite coeffs, a wrong
+ * struct_size, reserved != 0) leaves the instance as it was, a working stage included.  SELENITE_RX_DEVICE_ERROR is different: the old
+ * stage is released before the new rows are allocated, so a failed allocation leaves the instance with NO stage (as after f == NULL).
+ * selenite_rx_set_mode and every other setter leave it alone; selenite_rx_reset returns it to its state after set_tones and keeps the
+ * table.  Every process entry point runs it once per call (f32 and int16 slots, device and host pointers, the timing calls, global phase
+ * 1, selenite_rx_global_process_f32_device -- not phase 2).  With the stage on, the fused kernels run with their own AGC off and the
+ * generic AGC kernel finishes the call, as with NLMS.  With the stage off no launch, byte, allocation or output of any call changes. */
+int selenite_rx_set_tones(selenite_rx_instance *S, const selenite_rx_tones_config *f);
+/* Host copies of the state.  Drain the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the stage is off. */
+int selenite_rx_get_tones_state(selenite_rx_instance *S, const selenite_rx_tones_state_view *dst);
+int selenite_rx_set_tones_state(selenite_rx_instance *S, const selenite_rx_tones_state_view *src);
+/* Host copies of what a reader wants: tone [channels], power [channels][n_tones] of the last whole frame, frames = position /
+ * frame_blocks (whole frames since set_tones / reset).  NULL arguments are skipped.  Drains the instance's stream.
+ * SELENITE_RX_ARGUMENT_ERROR while the stage is off. */
+int selenite_rx_get_tones(selenite_rx_instance *S, uint32_t *tone, float *power, uint64_t *frames);
+/* The rows on the device, readable on the instance's stream behind a call (a tone-squelch gate will read `tone`); NULL while the stage is
+ * off; valid until the next selenite_rx_set_tones or selenite_rx_free. */
+const uint32_t *selenite_rx_tones_tone_device(const selenite_rx_instance *S);
+const float *selenite_rx_tones_power_device(const selenite_rx_instance *S);
+
 void *selenite_rx_device_alloc(size_t bytes);          /* hipMalloc; NULL on failure */
 void  selenite_rx_device_free(void *dptr);
 int   selenite_rx_memcpy_h2d(void *dptr, const void *hptr, size_t bytes);
@@ -787,6 +869,12 @@ int selenite_rx_design_biquad(float coeffs[5], int kind, double f0, double q, do
 /* FM de-emphasis, one pole: p = exp(-1 / tau_samples) (tau_samples > 0: the time constant in samples of the audio rate, 75 us at 12 kHz
  * is 0.9), {1 - p, 0, 0, p, 0}: unity gain at DC. */
 int selenite_rx_design_deemphasis(float coeffs[5], double tau_samples);
+
+/* The tone table of the tone-detector bank: coeffs [n_tones][3] = {2 cos w, cos w, sin w}, w = 2 pi freq[k], 0 < freq[k] < 0.5 cycles per
+ * sample of the audio rate.  Host only; computed in double, rounded once. */
+int selenite_rx_design_tones(float *coeffs, const double *freq, uint32_t n_tones);
+/* The 50 standard CTCSS frequencies in Hz, ascending, 67.0 .. 254.1; returns 50. */
+uint32_t selenite_rx_ctcss_hz(double hz[50]);
 
 int selenite_rx_abi_version(void);
 

@@ -133,3 +133,28 @@ extern "C" int selenite_rx_design_deemphasis(float coeffs[5], double tau_samples
     coeffs[4] = 0.0f;
     return SELENITE_RX_SUCCESS;
 }
+
+extern "C" int selenite_rx_design_tones(float *coeffs, const double *freq, uint32_t n_tones)
+{
+    if (!coeffs || !freq || n_tones == 0) return SELENITE_RX_ARGUMENT_ERROR;
+    for (uint32_t k = 0; k < n_tones; ++k)
+        if (!(freq[k] > 0.0 && freq[k] < 0.5)) return SELENITE_RX_ARGUMENT_ERROR;
+    for (uint32_t k = 0; k < n_tones; ++k) {
+        const double w = 2.0 * kPi * freq[k];
+        coeffs[3 * k] = (float)(2.0 * std::cos(w));
+        coeffs[3 * k + 1] = (float)std::cos(w);
+        coeffs[3 * k + 2] = (float)std::sin(w);
+    }
+    return SELENITE_RX_SUCCESS;
+}
+
+extern "C" uint32_t selenite_rx_ctcss_hz(double hz[50])
+{
+    static const double kCtcss[50] = { 67.0, 69.3, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9, 114.8,
+                                       118.8, 123.0, 127.3, 131.8, 136.5, 141.3, 146.2, 151.4, 156.7, 159.8, 162.2, 165.5, 167.9, 171.3, 173.8, 177.3,
+                                       179.9, 183.5, 186.2, 189.9, 192.8, 196.6, 199.5, 203.5, 206.5, 210.7, 218.1, 225.7, 229.1, 233.6, 241.8, 250.3,
+                                       254.1 };
+    if (hz)
+        for (int k = 0; k < 50; ++k) hz[k] = kCtcss[k];
+    return 50u;
+}

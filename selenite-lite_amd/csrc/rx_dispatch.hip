@@ -1,6 +1,6 @@
 // rx_dispatch.hip -- the one dispatcher behind every process entry point: which kernels serve a call, over which channels
-// (ChanRange), from which stream positions (CallStart).  The seven stages hook in here and nowhere else: the spectrum tap, the I/Q correction
-// and the noise blanker in front of the chain, the audio filter, NLMS and the level meter in front of the AGC (the meter's gate behind it), the output stage
+// (ChanRange), from which stream positions (CallStart).  The eight stages hook in here and nowhere else: the spectrum tap, the I/Q correction
+// and the noise blanker in front of the chain, the tone detector, the audio filter, NLMS and the level meter in front of the AGC (the meter's gate behind it), the output stage
 // behind the chain.
 #include "rx_host.h"
 
@@ -14,7 +14,7 @@ static SelCall call_facts(const selenite_rx_instance *S, uint32_t block_size, bo
     SelCall c;
     c.block_size = block_size; c.q15 = q15;
     c.global_gain = S->cfg.agc_enable && S->cfg.agc_global;
-    c.nr = S->nr.kind != SELENITE_RX_NR_OFF || S->meter.on || S->afilt.on;      // "un-scaled audio wanted in front of the AGC": NLMS, the level meter, the audio filter
+    c.nr = S->nr.kind != SELENITE_RX_NR_OFF || S->meter.on || S->afilt.on || S->tones.on;      // "un-scaled audio wanted in front of the AGC": NLMS, the level meter, the audio filter, the tone detector
     c.hist_ext = S->handover_repair && S->d_hist_ext;
     c.steps_uniform = S->steps_uniform; c.phase_uniform = S->phase_uniform; c.steps_grid256 = S->steps_grid256;
     c.no_shared_lo = S->no_shared_lo; c.no_periodic_lo = S->no_periodic_lo;
@@ -107,6 +107,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
     const int garith = arith == SELENITE_ARITH_AUTO ? SELENITE_ARITH_CMSIS : arith;      // the generic kernels: AUTO is bit-exact there
     const bool global = g.agc_enable && g.agc_global;
     const bool cw = mode_is_cw(g.mode) && g.n_biquad;
+    const bool tones = phase != kPhase2 && S->tones.on;                         // tone-detector bank, a tap behind the demodulator / CW filter (rx_tones.hip)
     const bool afilt = phase != kPhase2 && S->afilt.on;                         // audio biquad filter behind the demodulator / CW filter (rx_afilt.hip)
     const bool nr = phase != kPhase2 && S->nr.kind != SELENITE_RX_NR_OFF;      // NLMS stage in front of the AGC (rx_nlms.hip)
     const bool meter = phase != kPhase2 && S->meter.on;                         // level meter / squelch in front of the AGC (rx_meter.hip) ...
@@ -119,14 +120,15 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
     // a global gain get their input converted once, up front -- arm_q15_to_float over the whole buffer, the very operation the fused
     // int16 load performs -- and run as an f32-input call whose gain pass stores int16; round 2 left them to the generic kernels)
     // (the NLMS stage the same way: the fused kernel leaves un-scaled f32 audio, the stage runs in place on it, the AGC pass stores)
-    // (and the level meter, which reads that un-scaled audio, and the audio filter, which runs in place on it in front of both)
+    // (and the level meter, which reads that un-scaled audio, and the audio filter, which runs in place on it in front of both, and the
+    // tone detector, which reads it in front of all three)
     // (and int16 slots behind the I/Q correction, whose copy is f32: f32 in, int16 out -- the fused kernel with its AGC off into the f32
     // scratch, k_agc_generic applies the AGC and stores int16)
     const bool mixed = !src_q15 && dst_q15;
     const bool fusable = phase != kPhase2 && !S->force_generic;
     const bool ssb_fused = fusable && on_ssb_fused(S);
     const bool cw_fused = fusable && cw_fused_ok(g, block_size) && cw_strides_ok(p.in_stride, p.out_stride);    // (wider strides: the generic kernels)
-    if ((global || nr || meter || afilt) && src_q15 && (ssb_fused || cw_fused)) {
+    if ((global || nr || meter || afilt || tones) && src_q15 && (ssb_fused || cw_fused)) {
         // int16 values of the call (block_size % 4 == 0 for every fused shape), up to the end of the last channel's block_size samples: the
         // second part of a cut call (run_chain_core) starts inside the rows (= p.channels * p.in_stride * 2 when the call is not split)
         const size_t nval = ((size_t)(p.channels - 1) * p.in_stride + block_size) * 2;
@@ -139,7 +141,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
         }
     }
     float *audio = (float *)dst;      // un-scaled audio: dst itself when dst is f32, else scratch
-    if (dst_q15 && (global || nr || mixed || meter || afilt || !(ssb_fused || cw_fused))) {
+    if (dst_q15 && (global || nr || mixed || meter || afilt || tones || !(ssb_fused || cw_fused))) {
         const size_t need = (size_t)g.channels * p.out_stride * sizeof(float);
         int rc = ensure(S, (void **)&S->d_scratch, &S->scratch_bytes, need);
         if (rc) return rc;
@@ -201,7 +203,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
         }
         void *fdst = dst;
         bool fq15 = dst_q15;
-        if (global || nr || mixed || meter || afilt) {
+        if (global || nr || mixed || meter || afilt || tones) {
             pf.agc = 0; fdst = audio; fq15 = false;
             pf.out_cached = 1;                            // phase 2 (and, without block maxima from the kernel, the envelope fold) reads this audio back
             if (d.env_part) {                             // the kernel leaves the block maxima of every channel behind: folded below
@@ -214,13 +216,20 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
         }
         if (ssb_fused) HIPCHK(S, launch_fused(S->plan, pf, d, src, src_q15, fdst, fq15, S->delay_index, st));
         else HIPCHK(S, launch_cw_fused(pf, src, src_q15, fdst, fq15, st));
-        if (!global && !nr && !mixed && !meter && !afilt) return SELENITE_RX_SUCCESS;
+        if (!global && !nr && !mixed && !meter && !afilt && !tones) return SELENITE_RX_SUCCESS;
     }
 
     // generic path: front -> [biquad] -> AGC / convert
     if (phase != kPhase2 && !(ssb_fused || cw_fused)) {
         HIPCHK(S, launch_front_generic(p, garith, src, src_q15, audio, st));
         if (cw) HIPCHK(S, launch_biquad_generic(p, garith, audio, st));
+    }
+    // step 4-t: the tone detector reads the un-scaled audio of this launch.  Its frames are counted in DSP blocks of the stream: the second
+    // part of a cut call (run_chain_core: in_stride is the whole call, and the decision of the first part alone names its own length as
+    // the cut) starts behind the blocks of the first
+    if (tones) {
+        const uint32_t before = in_stride != block_size && d.first != block_size ? (in_stride - block_size) / g.block : 0u;
+        HIPCHK(S, launch_tones(S->tones.params(r, p, before), audio, st));
     }
     // step 4a: the audio filter in place on the un-scaled audio of this launch (a part of a cut call: its dst offset, the full stride)
     if (afilt) HIPCHK(S, launch_afilt(S->afilt.params(r, p), audio, st));
@@ -319,6 +328,7 @@ void srx::advance_streams(selenite_rx_instance *S, uint32_t block_size, Phase ph
     if (phase == kPhase2) return;
     if (S->cfg.nco_enable) S->phase_host += block_size * S->h_step[0];
     if (S->spec.len) S->spec.pos += block_size;
+    if (S->tones.on) S->tones.pos += block_size / S->cfg.block;
 }
 
 int srx::run_call(selenite_rx_instance *S, const void *src, bool src_q15, void *dst, bool dst_q15, uint32_t block_size, Phase phase, float *ext_env)

@@ -80,7 +80,7 @@ RxParams make_params(selenite_rx_instance *S, ChanRange r, uint32_t block_size);
 // enqueues one call over the channels of `r`; moves neither stream position
 int run_chain(selenite_rx_instance *S, ChanRange r, CallStart at, const void *src, bool src_q15, void *dst, bool dst_q15,
               uint32_t block_size, Phase phase, float *ext_env);
-// the one place the instance's phase_host and spec.pos advance: once per call, after its last launch is enqueued
+// the one place the instance's phase_host, spec.pos and tones.pos advance: once per call, after its last launch is enqueued
 void advance_streams(selenite_rx_instance *S, uint32_t block_size, Phase phase);
 // a device-pointer call over the whole instance: run_chain, then advance_streams
 int run_call(selenite_rx_instance *S, const void *src, bool src_q15, void *dst, bool dst_q15, uint32_t block_size, Phase phase, float *ext_env);

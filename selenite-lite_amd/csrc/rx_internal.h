@@ -341,6 +341,41 @@ struct __attribute__((visibility("hidden"))) AfiltStage {
     AfiltParams params(ChanRange r, const RxParams &p) const;   // the stage's view of a launch: the channels and the audio geometry of `p`
 };
 
+// ---- tone-detector bank (rx_tones.hip): K Goertzel recurrences and the frame energy per channel, a tap on the un-scaled audio behind the
+// demodulator and the CW filter, in front of the audio filter, NLMS, the meter and the AGC ----
+struct TonesParams {
+    uint32_t channels;     // channels of this launch (a ChanRange: the state rows are offset to it)
+    uint32_t nout;         // audio samples per channel in this launch: whole DSP blocks
+    uint32_t stride;       // audio samples between consecutive channels (RxParams::out_stride)
+    uint32_t n;            // audio samples per DSP block (block / decim)
+    uint32_t n_tones;      // K: 1 .. 64
+    uint32_t frame_blocks; // DSP blocks per frame
+    uint32_t fb0;          // DSP blocks of the running frame that lie in front of this launch: 0 .. frame_blocks - 1
+    uint32_t confirm, release;
+    float ratio, min_power;
+    const float *coeffs;   // [K][3] { 2 cos w, cos w, sin w }
+    float *s;              // [C][K][2] { s1, s2 }
+    float *energy;         // [C] the running frame's E
+    float *power;          // [C][K] of the last whole frame
+    float *frame_energy;   // [C] of the last whole frame
+    uint32_t *last_best, *tone, *cand, *run;
+    uint64_t *changes;
+};
+hipError_t launch_tones(const TonesParams &q, const float *audio, hipStream_t st);
+// the stage's part of the instance (selenite_rx_set_tones): on = false: no stage, no buffers
+struct __attribute__((visibility("hidden"))) TonesStage {
+    bool on = false;
+    uint32_t n_tones = 0, frame_blocks = 0, confirm = 0, rel = 0;
+    float ratio = 0.0f, min_power = 0.0f;
+    uint64_t pos = 0;                  // DSP blocks per channel since set_tones / reset: advanced once per call (rx_dispatch.hip: advance_streams)
+    float *d_coeffs = nullptr, *d_s = nullptr, *d_energy = nullptr, *d_power = nullptr, *d_frame_energy = nullptr;
+    uint32_t *d_last_best = nullptr, *d_tone = nullptr, *d_cand = nullptr, *d_run = nullptr;
+    uint64_t *d_changes = nullptr;
+    void release();                                         // frees the buffers: no stage
+    int init_state(selenite_rx_instance *S);                // the state set_tones leaves
+    TonesParams params(ChanRange r, const RxParams &p, uint32_t blocks_before) const;
+};
+
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
     SelPlan sel;                  // what select() reads: the shape (kind 0 = none), dense or not, which operands exist (rx_select.h)
@@ -434,6 +469,7 @@ struct selenite_rx_instance {
     int no_shared_lo = 0;              // SELENITE_RX_NO_SHARED_LO=1: always compute the LO per channel
     int no_periodic_lo = 0;            // SELENITE_RX_NO_PERIODIC_LO=1: never keep a periodic shared LO in registers
     int force_generic = 0;             // SELENITE_RX_FORCE_GENERIC=1 (tests cross-check both paths)
+    srx::TonesStage tones;             // tone-detector bank, a tap behind the demodulator / CW filter, in front of the audio filter (rx_tones.hip)
     srx::AfiltStage afilt;             // audio biquad filter, behind the demodulator / CW filter, in front of NLMS (rx_afilt.hip)
     srx::NrStage nr;                   // NLMS noise reduction / automatic notch, in front of the AGC (rx_nlms.hip)
     srx::MeterStage meter;             // signal-level meter and squelch, between NLMS and the AGC; its gate behind the AGC (rx_meter.hip)

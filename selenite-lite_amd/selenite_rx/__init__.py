@@ -129,6 +129,21 @@ class AfiltStateView(C.Structure):
 
 BIQUAD_NOTCH, BIQUAD_PEAKING, BIQUAD_LOWPASS, BIQUAD_HIGHPASS = 0, 1, 2, 3      # selenite_rx_design_biquad: kind
 
+
+class TonesConfig(C.Structure):
+    """struct selenite_rx_tones_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_tones", C.c_uint32), ("frame_blocks", C.c_uint32), ("confirm", C.c_uint32),
+                ("release", C.c_uint32), ("reserved", C.c_uint32), ("ratio", C.c_float), ("min_power", C.c_float), ("coeffs", f32p)]
+
+
+class TonesStateView(C.Structure):
+    """struct selenite_rx_tones_state_view."""
+    _fields_ = [("s", f32p), ("energy", f32p), ("power", f32p), ("frame_energy", f32p), ("last_best", u32p), ("tone", u32p), ("cand", u32p),
+                ("run", u32p), ("changes", u64p), ("position", u64p)]
+
+
+TONES_MAX, TONE_NONE = 64, 0xFFFFFFFF
+
 # every symbol include/selenite_rx.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "selenite_rx_init", "selenite_rx_free", "selenite_rx_set_mode", "selenite_rx_status",
@@ -156,6 +171,8 @@ ABI_SYMBOLS = [
     "selenite_rx_meter_open_device",
     "selenite_rx_set_afilt", "selenite_rx_set_afilt_coeffs", "selenite_rx_get_afilt_state", "selenite_rx_set_afilt_state",
     "selenite_rx_design_biquad", "selenite_rx_design_deemphasis",
+    "selenite_rx_set_tones", "selenite_rx_get_tones_state", "selenite_rx_set_tones_state", "selenite_rx_get_tones",
+    "selenite_rx_tones_tone_device", "selenite_rx_tones_power_device", "selenite_rx_design_tones", "selenite_rx_ctcss_hz",
 ]
 
 class TxConfig(C.Structure):
@@ -315,6 +332,18 @@ def lib():
             L.selenite_rx_set_afilt_state.argtypes = [vp, C.POINTER(AfiltStateView)]
             L.selenite_rx_design_biquad.argtypes = [f32p, C.c_int, C.c_double, C.c_double, C.c_double]
             L.selenite_rx_design_deemphasis.argtypes = [f32p, C.c_double]
+        if hasattr(L, "selenite_rx_set_tones"):             # (an older build named by SELENITE_RX_LIB lacks the tone detector)
+            L.selenite_rx_set_tones.argtypes = [vp, C.POINTER(TonesConfig)]
+            L.selenite_rx_get_tones_state.argtypes = [vp, C.POINTER(TonesStateView)]
+            L.selenite_rx_set_tones_state.argtypes = [vp, C.POINTER(TonesStateView)]
+            L.selenite_rx_get_tones.argtypes = [vp, C.POINTER(C.c_uint32), f32p, u64p]
+            L.selenite_rx_tones_tone_device.argtypes = [vp]
+            L.selenite_rx_tones_tone_device.restype = vp
+            L.selenite_rx_tones_power_device.argtypes = [vp]
+            L.selenite_rx_tones_power_device.restype = vp
+            L.selenite_rx_design_tones.argtypes = [f32p, C.POINTER(C.c_double), C.c_uint32]
+            L.selenite_rx_ctcss_hz.argtypes = [C.POINTER(C.c_double)]
+            L.selenite_rx_ctcss_hz.restype = C.c_uint32
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -356,6 +385,23 @@ def design_deemphasis(tau_samples):
     if rc:
         raise ValueError("selenite_rx_design_deemphasis: %d" % rc)
     return c
+
+
+def design_tones(freq):
+    """the tone table for Rx.set_tones: [K][3] {2 cos w, cos w, sin w}, w = 2 pi freq; freq in cycles per sample of the audio rate"""
+    f = np.ascontiguousarray(freq, np.float64).reshape(-1)
+    c = np.empty((f.size, 3), np.float32)
+    rc = lib().selenite_rx_design_tones(_fp(c), f.ctypes.data_as(C.POINTER(C.c_double)), f.size)
+    if rc:
+        raise ValueError("selenite_rx_design_tones: %d" % rc)
+    return c
+
+
+def ctcss_hz():
+    """the 50 standard CTCSS frequencies in Hz, ascending"""
+    hz = np.zeros(50, np.float64)
+    n = lib().selenite_rx_ctcss_hz(hz.ctypes.data_as(C.POINTER(C.c_double)))
+    return hz[:n]
 
 
 def design_interp(ni_taps, interp, cutoff):
@@ -1063,6 +1109,78 @@ class Rx:
         rc = self.L.selenite_rx_set_afilt_state(self.h, C.byref(v))
         if rc:
             raise RxError(rc, "selenite_rx_set_afilt_state")
+
+    # -- tone-detector bank (selenite_rx_set_tones) --------------------------------------------------
+    TONES_TYPES = dict(s=np.float32, energy=np.float32, power=np.float32, frame_energy=np.float32, last_best=np.uint32, tone=np.uint32,
+                       cand=np.uint32, run=np.uint32, changes=np.uint64, position=np.uint64)
+    TONES_PTRS = dict(s=f32p, energy=f32p, power=f32p, frame_energy=f32p, last_best=u32p, tone=u32p, cand=u32p, run=u32p, changes=u64p,
+                      position=u64p)
+
+    def set_tones(self, coeffs, frame_blocks=1, confirm=1, release=1, ratio=0.0, min_power=0.0):
+        """Put the tone-detector bank on the un-scaled audio of every channel (a tap in front of the audio filter, NLMS, the meter and the
+        AGC), or remove it (coeffs=None).  coeffs: [K][3] {2 cos w, cos w, sin w} (design_tones).  Puts the stage's state at its start.
+        Raises RxError on a bad field; the instance is then left as it was."""
+        old, self._tones = getattr(self, "_tones", None), None
+        if coeffs is None:
+            rc, new = self.L.selenite_rx_set_tones(self.h, None), None
+        else:
+            a = np.ascontiguousarray(coeffs, np.float32)
+            if a.ndim != 2 or a.shape[1] != 3:
+                self._tones = old
+                raise RxError(ARGUMENT_ERROR, "set_tones: coeffs is not [n_tones][3]")
+            g = TonesConfig()
+            g.struct_size, g.n_tones, g.frame_blocks, g.confirm, g.release, g.reserved = C.sizeof(TonesConfig), a.shape[0], int(frame_blocks), int(confirm), int(release), 0
+            g.ratio, g.min_power, g.coeffs = float(ratio), float(min_power), _fp(a)
+            rc, new = self.L.selenite_rx_set_tones(self.h, C.byref(g)), int(a.shape[0])
+        if rc == ARGUMENT_ERROR:
+            self._tones = old
+        if rc:
+            raise RxError(rc, self.L.selenite_rx_error_string(None).decode() if rc == ARGUMENT_ERROR else self.error())
+        self._tones = new
+
+    def _tones_shapes(self):
+        if getattr(self, "_tones", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the tone detector is off")
+        ch, k = self.cfg.channels, self._tones
+        return dict(s=(ch, k, 2), energy=(ch,), power=(ch, k), frame_energy=(ch,), last_best=(ch,), tone=(ch,), cand=(ch,), run=(ch,),
+                    changes=(ch,), position=(1,))
+
+    def tones_state(self):
+        """dict(s f32 [channels][K][2], energy, frame_energy f32 [channels], power f32 [channels][K], last_best, tone, cand, run u32
+        [channels], changes u64 [channels], position u64 [1]); drains the stream"""
+        a = {k: np.zeros(sh, self.TONES_TYPES[k]) for k, sh in self._tones_shapes().items()}
+        v = TonesStateView(*[a[k].ctypes.data_as(self.TONES_PTRS[k]) for k in self.TONES_TYPES])
+        rc = self.L.selenite_rx_get_tones_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_tones_state")
+        return a
+
+    def set_tones_state(self, d):
+        sh = self._tones_shapes()
+        a = {k: np.ascontiguousarray(d[k], self.TONES_TYPES[k]) for k in d}
+        for k in a:
+            assert a[k].shape == sh[k], (k, a[k].shape, sh[k])
+        v = TonesStateView(*[a[k].ctypes.data_as(self.TONES_PTRS[k]) if k in a else None for k in self.TONES_TYPES])
+        rc = self.L.selenite_rx_set_tones_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_set_tones_state")
+
+    def tones(self):
+        """(tone u32 [channels], power f32 [channels][K] of the last whole frame, whole frames since set_tones / reset); drains the stream"""
+        sh = self._tones_shapes()
+        tone, power, frames = np.zeros(sh["tone"], np.uint32), np.zeros(sh["power"], np.float32), C.c_uint64(0)
+        rc = self.L.selenite_rx_get_tones(self.h, tone.ctypes.data_as(u32p), _fp(power), C.byref(frames))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_tones")
+        return tone, power, int(frames.value)
+
+    def tones_tone_device(self):
+        """device address of the tone row (None while the stage is off)"""
+        return self.L.selenite_rx_tones_tone_device(self.h)
+
+    def tones_power_device(self):
+        """device address of the power rows (None while the stage is off)"""
+        return self.L.selenite_rx_tones_power_device(self.h)
 
     def close(self):
         if self.h:
