@@ -73,23 +73,29 @@ class Nlms:
 class Agc:
     """The AGC law per DSP block of `na` audio samples (oracle/rx_oracle.c, statement for statement; DESIGN.md "AGC"):
     env = max |a| (arm_abs_f32 + arm_max_f32), e = max(env, floor), d = target / e clamped to [gain_min, gain_max],
-    gain += rate * (d - gain) with rate = attack when the gain falls, decay otherwise; the block is scaled by the new gain."""
+    gain += rate * (d - gain) with rate = attack when the gain falls, decay otherwise; the block is scaled by the new gain.
+    agc_global: env = the maximum over all channels (orc_rx_process_f32_env); process(a, env=...) takes the blocks' maxima from the caller."""
 
-    def __init__(self, channels, na, params):
-        self.na = na
+    def __init__(self, channels, na, params, agc_global=False):
+        self.na, self.agc_global = na, agc_global
         p = {k: f32(v) for k, v in params.items()}
         self.p = p
         self.gain = np.full(channels, p["gain_init"], f32)
 
-    def process(self, a):
+    def process(self, a, env=None):
         a = np.asarray(a, f32)
         p, out = self.p, np.empty_like(a)
         g = self.gain
         for b0 in range(0, a.shape[1], self.na):
             blk = a[:, b0:b0 + self.na]
-            env = np.max(np.abs(blk), axis=1)
-            e = np.where(env < p["env_floor"], p["env_floor"], env)
-            d = np.divide(p["target"], e)
+            m = np.max(np.abs(blk), axis=1)
+            if self.agc_global:
+                m = np.full_like(m, m.max())
+            if env is not None:
+                m = np.full_like(m, f32(env[b0 // self.na]))
+            e = np.where(m < p["env_floor"], p["env_floor"], m)
+            with np.errstate(divide="ignore"):
+                d = np.divide(p["target"], e)          # (floor 0 and a silent block: +inf, clamped to gain_max below -- as the oracle)
             d = np.where(d > p["gain_max"], p["gain_max"], d)
             d = np.where(d < p["gain_min"], p["gain_min"], d)
             diff = np.subtract(d, g)
