@@ -250,13 +250,9 @@ extern "C" int selenite_rx_set_afilt(selenite_rx_instance *S, const selenite_rx_
             ncoef = (f->per_channel ? (size_t)S->cfg.channels : (size_t)1) * f->n_stages * 5;
             if (!all_finite(f->coeffs, ncoef)) bad = "a coefficient is not finite";
         }
-        if (bad) {
-            last_error() = std::string("selenite_rx_set_afilt: ") + bad;
-            return SELENITE_RX_ARGUMENT_ERROR;
-        }
+        if (bad) return refuse("selenite_rx_set_afilt", bad);
     }
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    if (int rc = drain(S)) return rc;                       // calls in flight still read the old stage
     AfiltStage &st = S->afilt;
     st.release();
     if (!f) return SELENITE_RX_SUCCESS;
@@ -283,10 +279,7 @@ extern "C" int selenite_rx_set_afilt_coeffs(selenite_rx_instance *S, uint32_t fi
         bad = st.per_channel ? "the channel range is not inside the instance" : "one coefficient set for all channels: the only range is (0, 1)";
     else if (!coeffs) bad = "coeffs is NULL";
     else if (!all_finite(coeffs, (size_t)n_channels * st.n_stages * 5)) bad = "a coefficient is not finite";
-    if (bad) {
-        last_error() = std::string("selenite_rx_set_afilt_coeffs: ") + bad;
-        return SELENITE_RX_ARGUMENT_ERROR;
-    }
+    if (bad) return refuse("selenite_rx_set_afilt_coeffs", bad);
     HIPCHK(S, hipSetDevice(S->device));
     // on the instance's stream: behind the calls issued so far, in front of the ones to come; drained, so the caller's array is free on return
     const size_t row = (size_t)st.n_stages * 5;
@@ -298,17 +291,11 @@ extern "C" int selenite_rx_set_afilt_coeffs(selenite_rx_instance *S, uint32_t fi
 static int afilt_state_copy(selenite_rx_instance *S, const selenite_rx_afilt_state_view *v, bool to_host)
 {
     if (!S || !v || !S->afilt.on) return SELENITE_RX_ARGUMENT_ERROR;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
-    AfiltStage &st = S->afilt;
+    const AfiltStage &st = S->afilt;
     const size_t C = S->cfg.channels;
     const size_t sbytes = C * st.n_stages * 4 * sizeof(float), cbytes = (st.per_channel ? C : 1) * st.n_stages * 5 * sizeof(float);
-    if (v->state) {
-        if (to_host) HIPCHK(S, hipMemcpy(v->state, st.d_state, sbytes, hipMemcpyDeviceToHost));
-        else HIPCHK(S, hipMemcpy(st.d_state, v->state, sbytes, hipMemcpyHostToDevice));
-    }
-    if (v->coeffs && to_host) HIPCHK(S, hipMemcpy(v->coeffs, st.d_coeffs, cbytes, hipMemcpyDeviceToHost));      // (set: selenite_rx_set_afilt_coeffs)
-    return SELENITE_RX_SUCCESS;
+    // (the coefficients are read only: selenite_rx_set_afilt_coeffs sets them)
+    return copy_rows(S, to_host, { { st.d_state, v->state, sbytes }, { st.d_coeffs, to_host ? v->coeffs : nullptr, cbytes } });
 }
 extern "C" int selenite_rx_get_afilt_state(selenite_rx_instance *S, const selenite_rx_afilt_state_view *v) { return afilt_state_copy(S, v, true); }
 extern "C" int selenite_rx_set_afilt_state(selenite_rx_instance *S, const selenite_rx_afilt_state_view *v) { return afilt_state_copy(S, v, false); }

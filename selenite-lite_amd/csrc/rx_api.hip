@@ -119,9 +119,7 @@ static int reset_state(selenite_rx_instance *S)
     if (S->d_rerun_flag) HIPCHK(S, hipMemsetAsync(S->d_rerun_flag, 0, C * sizeof(uint32_t), S->stream));
     if (S->d_rerun_list) HIPCHK(S, hipMemsetAsync(S->d_rerun_list, 0, 2 * sizeof(uint32_t), S->stream));      // both counters
     S->rerun_par = 0;
-    std::vector<float> gi(C, g.agc_gain_init);
-    HIPCHK(S, hipMemcpyAsync(S->d_gain, gi.data(), C * sizeof(float), hipMemcpyHostToDevice, S->stream));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
+    if (int rc = fill_rows(S, S->d_gain, C, &g.agc_gain_init)) return rc;      // (drains the stream)
     S->phase_uniform = true;
     S->phase_host = 0;
     if (int rc = S->tones.init_state(S)) return rc;
@@ -312,10 +310,7 @@ extern "C" void selenite_rx_free(selenite_rx_instance *S)
 extern "C" int selenite_rx_set_mode(selenite_rx_instance *S, uint8_t mode)
 {
     if (!S) return fail(nullptr, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_set_mode: S is NULL");
-    if (!mode_valid(mode, S->cfg.nh_taps)) {
-        last_error() = "selenite_rx_set_mode: unsupported mode";
-        return SELENITE_RX_ARGUMENT_ERROR;          // instance stays usable in its old mode
-    }
+    if (!mode_valid(mode, S->cfg.nh_taps)) return refuse("selenite_rx_set_mode", "unsupported mode");      // instance stays usable in its old mode
     S->cfg.mode = mode;
     HIPCHK(S, plan_fused(S->cfg, S->delay_is_impulse, S->hilb_odd_only, S->plan));
     return SELENITE_RX_SUCCESS;
@@ -513,40 +508,29 @@ extern "C" void selenite_rx_global_phase2_device(selenite_rx_instance *S, float 
 }
 
 // ------------------------------------------------------------------------------------------
+// the five arrays of selenite_rx_state_view copied out of the device (to_host) or into it; a row the configuration does not have is skipped
+static int chain_state_copy(selenite_rx_instance *S, const selenite_rx_state_view *v, bool to_host)
+{
+    const selenite_rx_config &g = S->cfg;
+    const size_t b = g.channels * sizeof(float);            // bytes of one word per channel
+    return copy_rows(S, to_host, { { S->d_dec_state, g.nd_taps > 1 ? v->dec_state : nullptr, b * 2 * (g.nd_taps - 1) },
+                                   { S->d_fir_state, g.nh_taps > 1 ? v->fir_state : nullptr, b * 2 * (g.nh_taps - 1) },
+                                   { S->d_biq_state, g.n_biquad ? v->biq_state : nullptr, b * 4 * g.n_biquad },
+                                   { S->d_gain, v->agc_gain, b }, { S->d_phase, v->nco_phase, b } });
+}
+
 extern "C" int selenite_rx_get_state(selenite_rx_instance *S, const selenite_rx_state_view *v)
 {
     if (!S || !v) return SELENITE_RX_ARGUMENT_ERROR;
-    const selenite_rx_config &g = S->cfg;
-    const size_t C = g.channels;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
-    if (v->dec_state && g.nd_taps > 1)
-        HIPCHK(S, hipMemcpy(v->dec_state, S->d_dec_state, C * 2 * (g.nd_taps - 1) * sizeof(float), hipMemcpyDeviceToHost));
-    if (v->fir_state && g.nh_taps > 1)
-        HIPCHK(S, hipMemcpy(v->fir_state, S->d_fir_state, C * 2 * (g.nh_taps - 1) * sizeof(float), hipMemcpyDeviceToHost));
-    if (v->biq_state && g.n_biquad)
-        HIPCHK(S, hipMemcpy(v->biq_state, S->d_biq_state, C * 4 * g.n_biquad * sizeof(float), hipMemcpyDeviceToHost));
-    if (v->agc_gain) HIPCHK(S, hipMemcpy(v->agc_gain, S->d_gain, C * sizeof(float), hipMemcpyDeviceToHost));
-    if (v->nco_phase) HIPCHK(S, hipMemcpy(v->nco_phase, S->d_phase, C * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return SELENITE_RX_SUCCESS;
+    return chain_state_copy(S, v, true);
 }
 
 extern "C" int selenite_rx_set_state(selenite_rx_instance *S, const selenite_rx_state_view *v)
 {
     if (!S || !v) return SELENITE_RX_ARGUMENT_ERROR;
-    const selenite_rx_config &g = S->cfg;
-    const size_t C = g.channels;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
-    if (v->dec_state && g.nd_taps > 1)
-        HIPCHK(S, hipMemcpy(S->d_dec_state, v->dec_state, C * 2 * (g.nd_taps - 1) * sizeof(float), hipMemcpyHostToDevice));
-    if (v->fir_state && g.nh_taps > 1)
-        HIPCHK(S, hipMemcpy(S->d_fir_state, v->fir_state, C * 2 * (g.nh_taps - 1) * sizeof(float), hipMemcpyHostToDevice));
-    if (v->biq_state && g.n_biquad)
-        HIPCHK(S, hipMemcpy(S->d_biq_state, v->biq_state, C * 4 * g.n_biquad * sizeof(float), hipMemcpyHostToDevice));
-    if (v->agc_gain) HIPCHK(S, hipMemcpy(S->d_gain, v->agc_gain, C * sizeof(float), hipMemcpyHostToDevice));
+    const size_t C = S->cfg.channels;
+    if (int rc = chain_state_copy(S, v, false)) return rc;
     if (v->nco_phase) {
-        HIPCHK(S, hipMemcpy(S->d_phase, v->nco_phase, C * sizeof(uint32_t), hipMemcpyHostToDevice));
         S->phase_uniform = true;
         for (size_t c = 1; c < C; ++c) S->phase_uniform = S->phase_uniform && v->nco_phase[c] == v->nco_phase[0];
         S->phase_host = v->nco_phase[0];

@@ -1,12 +1,25 @@
 // rx_dispatch.hip -- the one dispatcher behind every process entry point: which kernels serve a call, over which channels
-// (ChanRange), from which stream positions (CallStart).  The eight stages hook in here and nowhere else: the spectrum tap, the I/Q correction
-// and the noise blanker in front of the chain, the tone detector, the audio filter, NLMS and the level meter in front of the AGC (the meter's gate behind it), the output stage
-// behind the chain.
+// (ChanRange), from which stream positions (CallStart).  Two host-side functions decide, the launchers here execute: select() (rx_select.h)
+// names the kernel of a launch, route() (rx_route.h) its way through the stages -- which of them run, on which buffer, what finishes it.
+// The eight stages hook in here and nowhere else:
+//   run_front        the spectrum tap, the I/Q correction and the noise blanker in front of the chain;
+//   run_part         the tone detector, the audio filter, NLMS and the level meter in front of the AGC, the meter's gate behind it;
+//   with_out_stage   the output stage behind the chain.
+// A new stage in front of the AGC is one line in the route (its flag in StagesOn: it then counts in `unscaled`, and in what select() is told)
+// and one in the executor (its launch in run_part, at its place among the others); one in front of the chain is one line in run_front.
 #include "rx_host.h"
 
 #include <dlfcn.h>
 
 using namespace srx;
+
+// the stages in front of the AGC this instance has switched on
+static StagesOn stages_on(const selenite_rx_instance *S)
+{
+    StagesOn on;
+    on.tones = S->tones.on; on.afilt = S->afilt.on; on.nr = S->nr.kind != SELENITE_RX_NR_OFF; on.meter = S->meter.on;
+    return on;
+}
 
 // the facts select() (rx_select.h) wants of a call of block_size samples on this instance
 static SelCall call_facts(const selenite_rx_instance *S, uint32_t block_size, bool q15)
@@ -14,7 +27,7 @@ static SelCall call_facts(const selenite_rx_instance *S, uint32_t block_size, bo
     SelCall c;
     c.block_size = block_size; c.q15 = q15;
     c.global_gain = S->cfg.agc_enable && S->cfg.agc_global;
-    c.nr = S->nr.kind != SELENITE_RX_NR_OFF || S->meter.on || S->afilt.on || S->tones.on;      // "un-scaled audio wanted in front of the AGC": NLMS, the level meter, the audio filter, the tone detector
+    c.unscaled_stage = stages_on(S).any();
     c.hist_ext = S->handover_repair && S->d_hist_ext;
     c.steps_uniform = S->steps_uniform; c.phase_uniform = S->phase_uniform; c.steps_grid256 = S->steps_grid256;
     c.no_shared_lo = S->no_shared_lo; c.no_periodic_lo = S->no_periodic_lo;
@@ -92,45 +105,54 @@ bool srx::block_size_ok(selenite_rx_instance *S, uint32_t block_size, const char
     return true;
 }
 
-// The one dispatcher behind every process entry point.
-// (phase_now: the common NCO phase at the first sample of this launch; d: select() for this launch)
-static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uint32_t phase_now, const void *src, bool src_q15, void *dst, bool dst_q15,
-                    uint32_t block_size, Phase phase, float *ext_env, uint32_t in_stride, uint32_t out_stride)
+// Where a launch sits in its call: the samples of the call in front of it, and the whole call's length (what the caller's rows are apart).
+// An uncut call is the part { 0, block_size }.
+struct CallPart { uint32_t offset, total; };
+
+// what route() (rx_route.h) wants of a launch on this instance
+static RouteFacts route_facts(const selenite_rx_instance *S, Phase phase, bool src_q15, bool dst_q15, bool cw_kernel)
+{
+    const selenite_rx_config &g = S->cfg;
+    RouteFacts f;
+    f.phase = phase; f.src_q15 = src_q15; f.dst_q15 = dst_q15;
+    f.agc_enable = g.agc_enable; f.global = g.agc_enable && g.agc_global;
+    f.on = stages_on(S); f.gate = S->meter.on && S->meter.gate;
+    f.force_generic = S->force_generic; f.ssb_kernels = on_ssb_fused(S); f.cw_kernel = cw_kernel;
+    f.cw_biquads = mode_is_cw(g.mode) && g.n_biquad; f.words = S->d_rerun_flag != nullptr;
+    return f;
+}
+
+// The one executor behind every process entry point: one launch of block_size samples, the part `at` of a call whose buffers are src and
+// dst and whose first sample has the common NCO phase phase0.  d: select() for this launch; the route is decided here, once, and run top to
+// bottom.
+static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, CallPart at, uint32_t phase0, const void *src, bool src_q15, void *dst, bool dst_q15,
+                    uint32_t block_size, Phase phase, float *ext_env)
 {
     const selenite_rx_config &g = S->cfg;
     HIPCHK(S, hipSetDevice(S->device));
     RxParams p = make_params(S, r, block_size);
-    p.in_stride = in_stride; p.out_stride = out_stride;
+    // both buffers are addressed with the whole call's per-channel stride, from this part's first sample
+    p.in_stride = at.total; p.out_stride = at.total / g.decim;
+    src = static_cast<const char *>(src) + (size_t)at.offset * 2 * (src_q15 ? sizeof(int16_t) : sizeof(float));
+    dst = static_cast<char *>(dst) + (size_t)(at.offset / g.decim) * (dst_q15 ? sizeof(int16_t) : sizeof(float));
+    const uint32_t phase_now = phase0 + at.offset * S->h_step[0];
     if (front_generic_lds_bytes(p) > 64 * 1024 && !on_ssb_fused(S))
         return fail(S, SELENITE_RX_LENGTH_ERROR, "filter lengths exceed the LDS budget of the generic kernel");
     const int arith = (int)g.arith;
     const int garith = arith == SELENITE_ARITH_AUTO ? SELENITE_ARITH_CMSIS : arith;      // the generic kernels: AUTO is bit-exact there
-    const bool global = g.agc_enable && g.agc_global;
-    const bool cw = mode_is_cw(g.mode) && g.n_biquad;
-    const bool tones = phase != kPhase2 && S->tones.on;                         // tone-detector bank, a tap behind the demodulator / CW filter (rx_tones.hip)
-    const bool afilt = phase != kPhase2 && S->afilt.on;                         // audio biquad filter behind the demodulator / CW filter (rx_afilt.hip)
-    const bool nr = phase != kPhase2 && S->nr.kind != SELENITE_RX_NR_OFF;      // NLMS stage in front of the AGC (rx_nlms.hip)
-    const bool meter = phase != kPhase2 && S->meter.on;                         // level meter / squelch in front of the AGC (rx_meter.hip) ...
-    const bool gated = phase != kPhase1 && S->meter.on && S->meter.gate;        // ... and its gate behind it
     hipStream_t st = S->stream;
+    // (the fused CW kernel: not with wider strides, which the generic kernels take)
+    const bool cw_kernel = phase != kPhase2 && !S->force_generic && cw_fused_ok(g, block_size) && cw_strides_ok(p.in_stride, p.out_stride);
+    const Route t = route(route_facts(S, phase, src_q15, dst_q15, cw_kernel));
 
-    // Fused kernels serve the global-gain variant too: they run with their own AGC off (un-scaled
-    // audio out), then the envelope reduction and the gain pass below finish the call.
-    // (the fused kernels convert in and out symmetrically, and a global gain needs f32 audio between its two phases: int16 slots with
-    // a global gain get their input converted once, up front -- arm_q15_to_float over the whole buffer, the very operation the fused
-    // int16 load performs -- and run as an f32-input call whose gain pass stores int16; round 2 left them to the generic kernels)
-    // (the NLMS stage the same way: the fused kernel leaves un-scaled f32 audio, the stage runs in place on it, the AGC pass stores)
-    // (and the level meter, which reads that un-scaled audio, and the audio filter, which runs in place on it in front of both, and the
-    // tone detector, which reads it in front of all three)
-    // (and int16 slots behind the I/Q correction, whose copy is f32: f32 in, int16 out -- the fused kernel with its AGC off into the f32
-    // scratch, k_agc_generic applies the AGC and stores int16)
-    const bool mixed = !src_q15 && dst_q15;
-    const bool fusable = phase != kPhase2 && !S->force_generic;
-    const bool ssb_fused = fusable && on_ssb_fused(S);
-    const bool cw_fused = fusable && cw_fused_ok(g, block_size) && cw_strides_ok(p.in_stride, p.out_stride);    // (wider strides: the generic kernels)
-    if ((global || nr || meter || afilt || tones) && src_q15 && (ssb_fused || cw_fused)) {
+    // Un-scaled audio (Route::unscaled): the fused kernels serve such a launch with their own AGC off, and the stages, the envelope
+    // reduction and the gain pass below finish it.  They convert in and out symmetrically, and the audio between them and the tail is f32:
+    // int16 input is converted once, up front -- arm_q15_to_float over the whole buffer, the very operation the fused int16 load performs
+    // -- and the launch runs as an f32-input call whose gain pass stores int16.  (f32 in, int16 out -- behind the I/Q correction, whose
+    // copy is f32 -- the same way: into the f32 scratch, k_agc_generic applies the AGC and stores int16.)
+    if (t.convert_in) {
         // int16 values of the call (block_size % 4 == 0 for every fused shape), up to the end of the last channel's block_size samples: the
-        // second part of a cut call (run_chain_core) starts inside the rows (= p.channels * p.in_stride * 2 when the call is not split)
+        // second part of a cut call starts inside the rows (= p.channels * p.in_stride * 2 when the call is not cut)
         const size_t nval = ((size_t)(p.channels - 1) * p.in_stride + block_size) * 2;
         if (nval % 8 == 0) {
             int rc = ensure(S, (void **)&S->d_conv_in, &S->conv_in_bytes, nval * sizeof(float));
@@ -141,7 +163,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
         }
     }
     float *audio = (float *)dst;      // un-scaled audio: dst itself when dst is f32, else scratch
-    if (dst_q15 && (global || nr || mixed || meter || afilt || tones || !(ssb_fused || cw_fused))) {
+    if (t.audio_in_scratch) {
         const size_t need = (size_t)g.channels * p.out_stride * sizeof(float);
         int rc = ensure(S, (void **)&S->d_scratch, &S->scratch_bytes, need);
         if (rc) return rc;
@@ -149,9 +171,9 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
     }
     // step 4c: the gate bytes of this launch, [cfg.channels][blocks], indexed by absolute channel; phase 2 reads the ones its phase 1 left
     MeterParams mq{};
-    if (meter || gated) {
+    if (t.run.meter || t.gate) {
         const size_t need = (size_t)g.channels * (block_size / g.block);
-        if (meter) {
+        if (t.run.meter) {
             int rc = ensure(S, (void **)&S->meter.d_bits, &S->meter.bits_bytes, need);
             if (rc) return rc;
         } else if (S->meter.bits_bytes < need) {
@@ -163,7 +185,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
     // provenance words k_ssb_split16 reads at its next call say so)
     // (a channel the matrix kernel left with its samples gets its Hilbert-pair history recomputed in exact arithmetic first: the
     // generic / CW kernels read it -- advisor finding, round 3)
-    if (phase != kPhase2 && S->d_rerun_flag && !ssb_fused) {
+    if (t.clear_words) {
         uint32_t *words = S->d_rerun_flag + r.first;
         if (p.hist_ext) {
             RxParams ph = p;
@@ -173,7 +195,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
         HIPCHK(S, hipMemsetAsync(words, 0, p.channels * sizeof(uint32_t), st));
     }
     bool env_emitted = false;      // global gain: the fused kernel wrote the per-channel block maxima
-    if (ssb_fused || cw_fused) {
+    if (t.fused) {
         RxParams pf = p;
         pf.nco = d.nco_rx; pf.lo_period = d.lo_period;
         if (d.lo_n) {
@@ -190,7 +212,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
             }
             pf.lo = S->d_lo;
         }
-        if (arith == SELENITE_ARITH_AUTO && ssb_fused) {
+        if (arith == SELENITE_ARITH_AUTO && t.ssb_fused) {
             // the split16 kernel raises the rerun flag of the channels it guards and leaves their state alone; the bit-exact
             // kernel then recomputes the flagged channels (launch_fused)
             pf.rerun_flag = S->d_rerun_flag + r.first;
@@ -203,7 +225,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
         }
         void *fdst = dst;
         bool fq15 = dst_q15;
-        if (global || nr || mixed || meter || afilt || tones) {
+        if (t.fused_agc_off) {
             pf.agc = 0; fdst = audio; fq15 = false;
             pf.out_cached = 1;                            // phase 2 (and, without block maxima from the kernel, the envelope fold) reads this audio back
             if (d.env_part) {                             // the kernel leaves the block maxima of every channel behind: folded below
@@ -214,30 +236,24 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
                 env_emitted = true;
             }
         }
-        if (ssb_fused) HIPCHK(S, launch_fused(S->plan, pf, d, src, src_q15, fdst, fq15, S->delay_index, st));
+        if (t.ssb_fused) HIPCHK(S, launch_fused(S->plan, pf, d, src, src_q15, fdst, fq15, S->delay_index, st));
         else HIPCHK(S, launch_cw_fused(pf, src, src_q15, fdst, fq15, st));
-        if (!global && !nr && !mixed && !meter && !afilt && !tones) return SELENITE_RX_SUCCESS;
+        if (t.done_after_fused) return SELENITE_RX_SUCCESS;
     }
 
     // generic path: front -> [biquad] -> AGC / convert
-    if (phase != kPhase2 && !(ssb_fused || cw_fused)) {
-        HIPCHK(S, launch_front_generic(p, garith, src, src_q15, audio, st));
-        if (cw) HIPCHK(S, launch_biquad_generic(p, garith, audio, st));
-    }
+    if (t.generic_front) HIPCHK(S, launch_front_generic(p, garith, src, src_q15, audio, st));
+    if (t.biquad) HIPCHK(S, launch_biquad_generic(p, garith, audio, st));
     // step 4-t: the tone detector reads the un-scaled audio of this launch.  Its frames are counted in DSP blocks of the stream: the second
-    // part of a cut call (run_chain_core: in_stride is the whole call, and the decision of the first part alone names its own length as
-    // the cut) starts behind the blocks of the first
-    if (tones) {
-        const uint32_t before = in_stride != block_size && d.first != block_size ? (in_stride - block_size) / g.block : 0u;
-        HIPCHK(S, launch_tones(S->tones.params(r, p, before), audio, st));
-    }
+    // part of a cut call starts behind the blocks of the first
+    if (t.run.tones) HIPCHK(S, launch_tones(S->tones.params(r, p, at.offset / g.block), audio, st));
     // step 4a: the audio filter in place on the un-scaled audio of this launch (a part of a cut call: its dst offset, the full stride)
-    if (afilt) HIPCHK(S, launch_afilt(S->afilt.params(r, p), audio, st));
+    if (t.run.afilt) HIPCHK(S, launch_afilt(S->afilt.params(r, p), audio, st));
     // step 4b: NLMS in place on the un-scaled audio (phase 1 of a global gain: before the envelope)
-    if (nr) HIPCHK(S, launch_nlms(S->nr.params(r, p), S->nr.taps, audio, st));
+    if (t.run.nr) HIPCHK(S, launch_nlms(S->nr.params(r, p), S->nr.taps, audio, st));
     // step 4c: the level meter reads the same audio and leaves the gate of every block of this launch
-    if (meter) HIPCHK(S, launch_meter(mq, audio, st));
-    if (global) {
+    if (t.run.meter) HIPCHK(S, launch_meter(mq, audio, st));
+    if (t.env || t.apply) {
         float *env = ext_env;
         if (!env) {
             const size_t need = sizeof(float) * (block_size / g.block);
@@ -245,7 +261,7 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
             if (rc) return rc;
             env = S->d_env;
         }
-        if (phase != kPhase2) {
+        if (t.env) {
             if (env_emitted) {
                 HIPCHK(S, launch_env_fold(S->d_env_part, env, p.channels, block_size / g.block, st));
             } else {
@@ -255,60 +271,58 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, uin
                 HIPCHK(S, launch_env_global(p, audio, S->d_env_part, env, st));
             }
         }
-        if (phase != kPhase1) HIPCHK(S, launch_agc_apply_global(p, garith, audio, env, dst, dst_q15, st));
-    } else if (g.agc_enable || dst_q15) {
-        HIPCHK(S, launch_agc_generic(p, garith, audio, dst, dst_q15, st));
+        if (t.apply) HIPCHK(S, launch_agc_apply_global(p, garith, audio, env, dst, dst_q15, st));
     }
+    if (t.agc_generic) HIPCHK(S, launch_agc_generic(p, garith, audio, dst, dst_q15, st));
     // the gate, behind the AGC: zeros over the closed blocks of whatever this launch's dst is (with an output stage: its input)
-    if (gated) HIPCHK(S, launch_gate(mq, dst, dst_q15, st));
+    if (t.gate) HIPCHK(S, launch_gate(mq, dst, dst_q15, st));
     return SELENITE_RX_SUCCESS;
 }
 
 // Entry of every process call: decides once which kernel serves it (rx_select.h) and runs that.  A split-precision call that ends in a
-// partial pass too short for the matrix kernel is cut in two launches on the same streaming state, each decided as a call of its own;
-// both parts address the caller's buffers with the full per-channel stride.  The tail is shorter than a pass, which k_ssb_split16
+// partial pass too short for the matrix kernel is cut in two launches on the same streaming state, each decided as a call of its own and
+// told where it sits in the call (CallPart).  The tail is shorter than a pass, which k_ssb_split16
 // takes: under SELENITE_ARITH_SPLIT16 it runs there; under SELENITE_ARITH_AUTO it is too short to leave the repair rows behind and runs
 // on the bit-exact k_ssb_fused, from a history k_hist_exact repairs first.
-static int run_chain_core(selenite_rx_instance *S, ChanRange r, uint32_t phase_now, const void *src, bool src_q15, void *dst, bool dst_q15,
+static int run_chain_core(selenite_rx_instance *S, ChanRange r, uint32_t phase0, const void *src, bool src_q15, void *dst, bool dst_q15,
                           uint32_t block_size, Phase phase, float *ext_env)
 {
     const selenite_rx_config &g = S->cfg;
-    const uint32_t nout = block_size / g.decim;
     const bool ssb = phase != kPhase2 && on_ssb_fused(S);
     if (ssb && S->plan.sel.btab16)
         if (int rc = ensure_hist_ext(S)) return rc;
     SelCall c = call_facts(S, block_size, src_q15 && dst_q15);      // (f32 in, int16 out -- behind the I/Q correction -- is decided as the f32 call it runs as)
     const Decision d = select(g, ssb ? S->plan.sel : SelPlan{}, c);
-    if (!d.first) return run_part(S, r, d, phase_now, src, src_q15, dst, dst_q15, block_size, phase, ext_env, block_size, nout);
-    const uint32_t bs1 = d.first;
-    if (int rc = run_part(S, r, d, phase_now, src, src_q15, dst, dst_q15, bs1, kAll, nullptr, block_size, nout)) return rc;
-    const size_t ein = src_q15 ? sizeof(int16_t) : sizeof(float), eout = dst_q15 ? sizeof(int16_t) : sizeof(float);
-    const char *src2 = static_cast<const char *>(src) + (size_t)bs1 * 2 * ein;
-    char *dst2 = static_cast<char *>(dst) + (size_t)(bs1 / g.decim) * eout;
-    c.block_size = block_size - bs1;
-    return run_part(S, r, select(g, S->plan.sel, c), phase_now + bs1 * S->h_step[0], src2, src_q15, dst2, dst_q15, c.block_size, kAll, nullptr, block_size, nout);
+    if (!d.first) return run_part(S, r, d, CallPart{ 0u, block_size }, phase0, src, src_q15, dst, dst_q15, block_size, phase, ext_env);
+    if (int rc = run_part(S, r, d, CallPart{ 0u, block_size }, phase0, src, src_q15, dst, dst_q15, d.first, kAll, nullptr)) return rc;
+    c.block_size = block_size - d.first;
+    return run_part(S, r, select(g, S->plan.sel, c), CallPart{ d.first, block_size }, phase0, src, src_q15, dst, dst_q15, c.block_size, kAll, nullptr);
 }
 
-// With an output stage the chain runs exactly as without one, into the instance's f32 audio buffer, and the stage kernel writes the caller's dst.
+// The taps and copies in front of the chain, in this order on the stream: the spectrum tap reads the caller's own input, the I/Q
+// correction (step 0b2) writes a corrected f32 copy of it, the noise blanker (step 0c) a blanked copy of that; from here on the call reads
+// *src, in the format *src_q15 says.  A new stage in front of the chain is one line here.
+static int run_front(selenite_rx_instance *S, ChanRange r, uint64_t spec_pos, const void **src, bool *src_q15, uint32_t block_size)
+{
+    if (S->spec.len)
+        if (int rc = S->spec.run(S, r, spec_pos, *src, *src_q15, block_size)) return rc;
+    if (S->iqc.frame) {
+        if (int rc = S->iqc.run(S, r, *src, *src_q15, block_size, src)) return rc;
+        *src_q15 = false;
+    }
+    if (S->nb.frame)
+        if (int rc = S->nb.run(S, r, *src, *src_q15, block_size, src)) return rc;
+    return SELENITE_RX_SUCCESS;
+}
+
+// The output stage's side of a call, around `chain(src, src_q15, dst, dst_q15)`.  Without a stage that is the chain on the caller's dst.
+// With one the chain runs exactly as without, into the instance's f32 audio buffer, and the stage kernel writes the caller's dst.
 // int16 slots: the fused kernels convert in and out symmetrically, so the input is converted up front (arm_q15_to_float over the whole
 // buffer, the operation the fused int16 load performs) and the call runs as an f32 call whose stage stores int16.
-int srx::run_chain(selenite_rx_instance *S, ChanRange r, CallStart at, const void *src, bool src_q15, void *dst, bool dst_q15,
-                   uint32_t block_size, Phase phase, float *ext_env)
+template <typename Chain>
+static int with_out_stage(selenite_rx_instance *S, ChanRange r, const void *src, bool src_q15, void *dst, bool dst_q15, uint32_t block_size, Chain chain)
 {
-    // an invariant, checked before anything is launched: both split entry points (rx_api.hip) refuse such an instance themselves, with
-    // their own message, so no C-ABI call gets here
-    if (S->out.on && phase != kAll) return fail(S, SELENITE_RX_ARGUMENT_ERROR, "the split global-gain calls exchange audio at the decimated rate: not with an output stage");
-    if (S->spec.len && phase != kPhase2)
-        if (int rc = S->spec.run(S, r, at.spec_pos, src, src_q15, block_size)) return rc;
-    // step 0b2: from here on the call reads the corrected f32 copy of the input (the tap above has read the caller's own)
-    if (S->iqc.frame && phase != kPhase2) {
-        if (int rc = S->iqc.run(S, r, src, src_q15, block_size, &src)) return rc;
-        src_q15 = false;
-    }
-    // step 0c: from here on the chain reads the blanked copy of the input (the tap above has read the caller's own)
-    if (S->nb.frame && phase != kPhase2)
-        if (int rc = S->nb.run(S, r, src, src_q15, block_size, &src)) return rc;
-    if (!S->out.on) return run_chain_core(S, r, at.phase, src, src_q15, dst, dst_q15, block_size, phase, ext_env);
+    if (!S->out.on) return chain(src, src_q15, dst, dst_q15);
     HIPCHK(S, hipSetDevice(S->device));
     float *audio = nullptr;
     if (int rc = S->out.audio_buffer(S, r, block_size, &audio)) return rc;
@@ -318,8 +332,21 @@ int srx::run_chain(selenite_rx_instance *S, ChanRange r, CallStart at, const voi
         HIPCHK(S, launch_q15_to_f32(static_cast<const int16_t *>(src), S->d_conv_in, nval, S->stream));
         src = S->d_conv_in;
     }
-    if (int rc = run_chain_core(S, r, at.phase, src, false, audio, false, block_size, kAll, nullptr)) return rc;
+    if (int rc = chain(src, false, audio, false)) return rc;
     return S->out.run(S, r, audio, dst, dst_q15, block_size);
+}
+
+int srx::run_chain(selenite_rx_instance *S, ChanRange r, CallStart at, const void *src, bool src_q15, void *dst, bool dst_q15,
+                   uint32_t block_size, Phase phase, float *ext_env)
+{
+    // an invariant, checked before anything is launched: both split entry points (rx_api.hip) refuse such an instance themselves, with
+    // their own message, so no C-ABI call gets here
+    if (S->out.on && phase != kAll) return fail(S, SELENITE_RX_ARGUMENT_ERROR, "the split global-gain calls exchange audio at the decimated rate: not with an output stage");
+    if (phase != kPhase2)
+        if (int rc = run_front(S, r, at.spec_pos, &src, &src_q15, block_size)) return rc;
+    return with_out_stage(S, r, src, src_q15, dst, dst_q15, block_size, [&](const void *in, bool in_q15, void *out, bool out_q15) {
+        return run_chain_core(S, r, at.phase, in, in_q15, out, out_q15, block_size, phase, ext_env);
+    });
 }
 
 // global_phase2 advances nothing (its phase 1 did); the NCO phase moves only when the NCO runs
@@ -369,23 +396,20 @@ extern "C" int selenite_rx_global_process_f32_device(selenite_rx_instance *S, co
     // (an output stage sits behind phase 2: both phases work on the instance's audio buffer, the stage writes dDstAudio)
     const ChanRange r = all_channels(S);
     const CallStart at = call_start(S);
-    float *audio = dDstAudio;
-    if (S->out.on && (rc = S->out.audio_buffer(S, r, blockSize, &audio))) return rc;
-    if (S->spec.len && (rc = S->spec.run(S, r, at.spec_pos, dSrcIQ, false, blockSize))) return rc;
     const void *in = dSrcIQ;
-    if (S->iqc.frame && (rc = S->iqc.run(S, r, in, false, blockSize, &in))) return rc;
-    if (S->nb.frame && (rc = S->nb.run(S, r, in, false, blockSize, &in))) return rc;
-    rc = run_chain_core(S, r, at.phase, in, false, audio, false, blockSize, kPhase1, S->d_env);
-    if (rc) return rc;
-    if (rccl_comm) {                                        // NULL: single rank, nothing to exchange
-        nccl_allreduce_fn ar = rccl_allreduce();
-        if (!ar) return fail(S, SELENITE_RX_DEVICE_ERROR, "selenite_rx_global_process_f32_device: RCCL (ncclAllReduce) is not available");
-        const int nccl_float = 7, nccl_max = 2;             // ncclFloat32, ncclMax (rccl.h)
-        const int e = ar(S->d_env, S->d_env, nblk, nccl_float, nccl_max, rccl_comm, S->stream);
-        if (e != 0) return fail(S, SELENITE_RX_DEVICE_ERROR, "selenite_rx_global_process_f32_device: ncclAllReduce failed (" + std::to_string(e) + ")");
-    }
-    rc = run_chain_core(S, r, at.phase, nullptr, false, audio, false, blockSize, kPhase2, S->d_env);
-    if (!rc && S->out.on) rc = S->out.run(S, r, audio, dDstAudio, false, blockSize);
+    bool in_q15 = false;
+    if ((rc = run_front(S, r, at.spec_pos, &in, &in_q15, blockSize))) return rc;
+    rc = with_out_stage(S, r, in, in_q15, dDstAudio, false, blockSize, [&](const void *src, bool, void *audio, bool) {
+        if (int e = run_chain_core(S, r, at.phase, src, false, audio, false, blockSize, kPhase1, S->d_env)) return e;
+        if (rccl_comm) {                                    // NULL: single rank, nothing to exchange
+            nccl_allreduce_fn ar = rccl_allreduce();
+            if (!ar) return fail(S, SELENITE_RX_DEVICE_ERROR, "selenite_rx_global_process_f32_device: RCCL (ncclAllReduce) is not available");
+            const int nccl_float = 7, nccl_max = 2;         // ncclFloat32, ncclMax (rccl.h)
+            const int e = ar(S->d_env, S->d_env, nblk, nccl_float, nccl_max, rccl_comm, S->stream);
+            if (e != 0) return fail(S, SELENITE_RX_DEVICE_ERROR, "selenite_rx_global_process_f32_device: ncclAllReduce failed (" + std::to_string(e) + ")");
+        }
+        return run_chain_core(S, r, at.phase, nullptr, false, audio, false, blockSize, kPhase2, S->d_env);
+    });
     if (rc) return rc;
     advance_streams(S, blockSize, kAll);
     return SELENITE_RX_SUCCESS;

@@ -2,7 +2,11 @@
 // interfaces between rx_api.hip (instance, accessors, entry points), rx_dispatch.hip (the dispatcher), rx_hostpipe.hip (host-pointer
 // calls), rx_timing.hip and the stages' own files.  Host code only; not part of the C-ABI.
 #pragma once
+#include <initializer_list>
+#include <vector>
+
 #include "rx_internal.h"
+#include "rx_route.h"
 
 // (hidden: these are interfaces between the library's own translation units, none of them an exported name)
 #pragma GCC visibility push(hidden)
@@ -28,6 +32,14 @@ inline int fail(selenite_rx_instance *S, int code, const std::string &msg)
             return srx::fail((S), SELENITE_RX_DEVICE_ERROR,                                 \
                              std::string(#call) + ": " + hipGetErrorString(e_));            \
     } while (0)
+
+// a refused configuration (the set_* calls): the calling thread's last error says why; the instance's status and error string stay as
+// they are, so it goes on as it was
+inline int refuse(const char *who, const char *why, int code = SELENITE_RX_ARGUMENT_ERROR)
+{
+    last_error() = std::string(who) + ": " + why;
+    return code;
+}
 
 // ---- device buffers ----
 template <typename T>
@@ -63,10 +75,39 @@ inline int ensure(selenite_rx_instance *S, void **buf, size_t *cap, size_t need)
     *cap = need;
     return SELENITE_RX_SUCCESS;
 }
+// the instance's device, and its stream drained: in front of every read or write of state from the host
+inline int drain(selenite_rx_instance *S)
+{
+    HIPCHK(S, hipSetDevice(S->device));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    return SELENITE_RX_SUCCESS;
+}
+// State rows copied out of the device (to_host) or into it, behind one drain.  A row whose host pointer is NULL is skipped: the caller of
+// a *_state call did not ask for it, or it does not exist, or it is not copied in this direction.
+struct Row { void *dev; const void *host; size_t bytes; };
+inline int copy_rows(selenite_rx_instance *S, bool to_host, std::initializer_list<Row> rows)
+{
+    if (int rc = drain(S)) return rc;
+    for (const Row &w : rows) {
+        if (!w.host) continue;
+        if (to_host) HIPCHK(S, hipMemcpy(const_cast<void *>(w.host), w.dev, w.bytes, hipMemcpyDeviceToHost));
+        else HIPCHK(S, hipMemcpy(w.dev, w.host, w.bytes, hipMemcpyHostToDevice));
+    }
+    return SELENITE_RX_SUCCESS;
+}
+// A per-channel row filled with one value (n = 1) or with one row of n values per channel, on the instance's stream: everything enqueued
+// before it has run on return (the host vector lives until then).
+template <typename T>
+inline int fill_rows(selenite_rx_instance *S, T *dev, size_t channels, const T *value, size_t n = 1)
+{
+    std::vector<T> h(channels * n);
+    for (size_t i = 0; i < h.size(); ++i) h[i] = value[i % n];
+    HIPCHK(S, hipMemcpyAsync(dev, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, S->stream));
+    HIPCHK(S, hipStreamSynchronize(S->stream));
+    return SELENITE_RX_SUCCESS;
+}
 
-// ---- the dispatcher (rx_dispatch.hip) ----
-enum Phase { kAll, kPhase1, kPhase2 };
-
+// ---- the dispatcher (rx_dispatch.hip; Phase and the route of a launch: rx_route.h) ----
 // Where a call starts in the two streams the host tracks: the common NCO phase (valid while every channel shares step and phase) and the
 // spectrum tap's position.  Read once per call and handed down: every channel chunk of a host-pointer call starts from the same one.
 struct CallStart { uint32_t phase; uint64_t spec_pos; };

@@ -262,14 +262,11 @@ int IqcStage::init_state(selenite_rx_instance *S)
 {
     if (!frame) return SELENITE_RX_SUCCESS;
     const size_t C = S->cfg.channels;
-    const std::vector<float> di(C, dc_i_init), dq(C, dc_q_init), hp(C, p_init), hg(C, g_init);
-    HIPCHK(S, hipMemcpyAsync(d_dc_i, di.data(), C * sizeof(float), hipMemcpyHostToDevice, S->stream));
-    HIPCHK(S, hipMemcpyAsync(d_dc_q, dq.data(), C * sizeof(float), hipMemcpyHostToDevice, S->stream));
-    HIPCHK(S, hipMemcpyAsync(d_p, hp.data(), C * sizeof(float), hipMemcpyHostToDevice, S->stream));
-    HIPCHK(S, hipMemcpyAsync(d_g, hg.data(), C * sizeof(float), hipMemcpyHostToDevice, S->stream));
     HIPCHK(S, hipMemsetAsync(d_held, 0, C * sizeof(uint64_t), S->stream));
-    HIPCHK(S, hipStreamSynchronize(S->stream));             // (the host vectors above live until here)
-    return SELENITE_RX_SUCCESS;
+    if (int rc = fill_rows(S, d_dc_i, C, &dc_i_init)) return rc;
+    if (int rc = fill_rows(S, d_dc_q, C, &dc_q_init)) return rc;
+    if (int rc = fill_rows(S, d_p, C, &p_init)) return rc;
+    return fill_rows(S, d_g, C, &g_init);                   // (each of them drains the stream)
 }
 
 // Step 0b2: one launch on the instance's stream writes the corrected copy of the call's input, always f32 and with the caller's stride
@@ -315,13 +312,9 @@ extern "C" int selenite_rx_set_iqc(selenite_rx_instance *S, const selenite_rx_iq
         else if (!(iqc->p_init >= -iqc->p_max && iqc->p_init <= iqc->p_max)) bad = "p_init is not within +-p_max";
         else if (!(iqc->g_init >= g_min && iqc->g_init <= iqc->g_max)) bad = "g_init is not within [1 / g_max, g_max]";
         else if (!std::isfinite(iqc->dc_i_init) || !std::isfinite(iqc->dc_q_init)) bad = "dc_i_init / dc_q_init is not finite";
-        if (bad) {
-            last_error() = std::string("selenite_rx_set_iqc: ") + bad;
-            return code;
-        }
+        if (bad) return refuse("selenite_rx_set_iqc", bad, code);
     }
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    if (int rc = drain(S)) return rc;                       // calls in flight still read the old stage
     IqcStage &st = S->iqc;
     st.release();
     if (!iqc) return SELENITE_RX_SUCCESS;
@@ -345,22 +338,10 @@ extern "C" int selenite_rx_set_iqc(selenite_rx_instance *S, const selenite_rx_iq
 static int iqc_state_copy(selenite_rx_instance *S, const selenite_rx_iqc_state_view *v, bool to_host)
 {
     if (!S || !v || !S->iqc.frame) return SELENITE_RX_ARGUMENT_ERROR;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
-    IqcStage &st = S->iqc;
+    const IqcStage &st = S->iqc;
     const size_t C = S->cfg.channels;
-    float *const dev[4] = { st.d_dc_i, st.d_dc_q, st.d_p, st.d_g };
-    float *const host[4] = { v->dc_i, v->dc_q, v->p, v->g };
-    for (int k = 0; k < 4; ++k) {
-        if (!host[k]) continue;
-        if (to_host) HIPCHK(S, hipMemcpy(host[k], dev[k], C * sizeof(float), hipMemcpyDeviceToHost));
-        else HIPCHK(S, hipMemcpy(dev[k], host[k], C * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (v->held) {
-        if (to_host) HIPCHK(S, hipMemcpy(v->held, st.d_held, C * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        else HIPCHK(S, hipMemcpy(st.d_held, v->held, C * sizeof(uint64_t), hipMemcpyHostToDevice));
-    }
-    return SELENITE_RX_SUCCESS;
+    return copy_rows(S, to_host, { { st.d_dc_i, v->dc_i, C * sizeof(float) }, { st.d_dc_q, v->dc_q, C * sizeof(float) }, { st.d_p, v->p, C * sizeof(float) },
+                                   { st.d_g, v->g, C * sizeof(float) }, { st.d_held, v->held, C * sizeof(uint64_t) } });
 }
 extern "C" int selenite_rx_get_iqc_state(selenite_rx_instance *S, const selenite_rx_iqc_state_view *v) { return iqc_state_copy(S, v, true); }
 extern "C" int selenite_rx_set_iqc_state(selenite_rx_instance *S, const selenite_rx_iqc_state_view *v) { return iqc_state_copy(S, v, false); }

@@ -180,14 +180,11 @@ int MeterStage::init_state(selenite_rx_instance *S)
 {
     if (!on) return SELENITE_RX_SUCCESS;
     const size_t C = S->cfg.channels;
-    const std::vector<float> lv(C, level_init);
-    HIPCHK(S, hipMemcpyAsync(d_level, lv.data(), C * sizeof(float), hipMemcpyHostToDevice, S->stream));
     HIPCHK(S, hipMemsetAsync(d_open, 0, C * sizeof(uint32_t), S->stream));
     HIPCHK(S, hipMemsetAsync(d_hold, 0, C * sizeof(uint32_t), S->stream));
     HIPCHK(S, hipMemsetAsync(d_opens, 0, C * sizeof(uint64_t), S->stream));
     HIPCHK(S, hipMemsetAsync(d_open_blocks, 0, C * sizeof(uint64_t), S->stream));
-    HIPCHK(S, hipStreamSynchronize(S->stream));             // (the host vector above lives until here)
-    return SELENITE_RX_SUCCESS;
+    return fill_rows(S, d_level, C, &level_init);           // (drains the stream)
 }
 
 // the stage's view of a launch: the channels and the audio geometry of `p`; the state rows and the gate bytes move with the range
@@ -224,13 +221,9 @@ extern "C" int selenite_rx_set_meter(selenite_rx_instance *S, const selenite_rx_
         else if (m->sense == SELENITE_RX_SQ_ABOVE && !(m->close_level <= m->open_level)) bad = "SELENITE_RX_SQ_ABOVE: close_level is above open_level";
         else if (m->sense == SELENITE_RX_SQ_BELOW && !(m->close_level >= m->open_level)) bad = "SELENITE_RX_SQ_BELOW: close_level is below open_level";
         else if (!(std::isfinite(m->level_init) && m->level_init >= 0.0f)) bad = "level_init is not finite and >= 0";
-        if (bad) {
-            last_error() = std::string("selenite_rx_set_meter: ") + bad;
-            return SELENITE_RX_ARGUMENT_ERROR;
-        }
+        if (bad) return refuse("selenite_rx_set_meter", bad);
     }
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    if (int rc = drain(S)) return rc;                       // calls in flight still read the old stage
     MeterStage &st = S->meter;
     st.release();
     if (!m) return SELENITE_RX_SUCCESS;
@@ -253,19 +246,11 @@ extern "C" int selenite_rx_set_meter(selenite_rx_instance *S, const selenite_rx_
 static int meter_state_copy(selenite_rx_instance *S, const selenite_rx_meter_state_view *v, bool to_host)
 {
     if (!S || !v || !S->meter.on) return SELENITE_RX_ARGUMENT_ERROR;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
-    MeterStage &st = S->meter;
+    const MeterStage &st = S->meter;
     const size_t C = S->cfg.channels;
-    void *const dev[5] = { st.d_level, st.d_open, st.d_hold, st.d_opens, st.d_open_blocks };
-    void *const host[5] = { v->level, v->open, v->hold, v->opens, v->open_blocks };
-    const size_t bytes[5] = { C * sizeof(float), C * sizeof(uint32_t), C * sizeof(uint32_t), C * sizeof(uint64_t), C * sizeof(uint64_t) };
-    for (int k = 0; k < 5; ++k) {
-        if (!host[k]) continue;
-        if (to_host) HIPCHK(S, hipMemcpy(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost));
-        else HIPCHK(S, hipMemcpy(dev[k], host[k], bytes[k], hipMemcpyHostToDevice));
-    }
-    return SELENITE_RX_SUCCESS;
+    return copy_rows(S, to_host, { { st.d_level, v->level, C * sizeof(float) }, { st.d_open, v->open, C * sizeof(uint32_t) },
+                                   { st.d_hold, v->hold, C * sizeof(uint32_t) }, { st.d_opens, v->opens, C * sizeof(uint64_t) },
+                                   { st.d_open_blocks, v->open_blocks, C * sizeof(uint64_t) } });
 }
 extern "C" int selenite_rx_get_meter_state(selenite_rx_instance *S, const selenite_rx_meter_state_view *v) { return meter_state_copy(S, v, true); }
 extern "C" int selenite_rx_set_meter_state(selenite_rx_instance *S, const selenite_rx_meter_state_view *v) { return meter_state_copy(S, v, false); }

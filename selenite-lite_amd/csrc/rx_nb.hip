@@ -208,11 +208,10 @@ int NbStage::init_state(selenite_rx_instance *S)
 {
     if (!frame) return SELENITE_RX_SUCCESS;
     const size_t C = S->cfg.channels;
-    HIPCHK(S, hipMemsetAsync(d_level, 0, C * sizeof(float), S->stream));
+    const float unprimed = 0.0f;
     HIPCHK(S, hipMemsetAsync(d_blanked, 0, C * sizeof(uint64_t), S->stream));
     HIPCHK(S, hipMemsetAsync(d_bursts, 0, C * sizeof(uint64_t), S->stream));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
-    return SELENITE_RX_SUCCESS;
+    return fill_rows(S, d_level, C, &unprimed);             // (drains the stream)
 }
 
 // Step 0c: one launch on the instance's stream writes the blanked copy of the call's input, in the caller's format and with the caller's
@@ -252,13 +251,9 @@ extern "C" int selenite_rx_set_nb(selenite_rx_instance *S, const selenite_rx_nb_
         else if (!(std::isfinite(nb->threshold) && nb->threshold >= 1.0f)) bad = "threshold is not finite and >= 1";
         else if (!(nb->alpha > 0.0f && nb->alpha <= 1.0f)) bad = "alpha is not in (0, 1]";
         else if (!(std::isfinite(nb->clamp) && nb->clamp >= 1.0f)) bad = "clamp is not finite and >= 1";
-        if (bad) {
-            last_error() = std::string("selenite_rx_set_nb: ") + bad;
-            return code;
-        }
+        if (bad) return refuse("selenite_rx_set_nb", bad, code);
     }
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    if (int rc = drain(S)) return rc;                       // calls in flight still read the old stage
     NbStage &st = S->nb;
     st.release();
     if (!nb) return SELENITE_RX_SUCCESS;
@@ -278,20 +273,10 @@ extern "C" int selenite_rx_set_nb(selenite_rx_instance *S, const selenite_rx_nb_
 static int nb_state_copy(selenite_rx_instance *S, const selenite_rx_nb_state_view *v, bool to_host)
 {
     if (!S || !v || !S->nb.frame) return SELENITE_RX_ARGUMENT_ERROR;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
-    NbStage &st = S->nb;
+    const NbStage &st = S->nb;
     const size_t C = S->cfg.channels;
-    if (to_host) {
-        if (v->level) HIPCHK(S, hipMemcpy(v->level, st.d_level, C * sizeof(float), hipMemcpyDeviceToHost));
-        if (v->blanked) HIPCHK(S, hipMemcpy(v->blanked, st.d_blanked, C * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        if (v->bursts) HIPCHK(S, hipMemcpy(v->bursts, st.d_bursts, C * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    } else {
-        if (v->level) HIPCHK(S, hipMemcpy(st.d_level, v->level, C * sizeof(float), hipMemcpyHostToDevice));
-        if (v->blanked) HIPCHK(S, hipMemcpy(st.d_blanked, v->blanked, C * sizeof(uint64_t), hipMemcpyHostToDevice));
-        if (v->bursts) HIPCHK(S, hipMemcpy(st.d_bursts, v->bursts, C * sizeof(uint64_t), hipMemcpyHostToDevice));
-    }
-    return SELENITE_RX_SUCCESS;
+    return copy_rows(S, to_host, { { st.d_level, v->level, C * sizeof(float) }, { st.d_blanked, v->blanked, C * sizeof(uint64_t) },
+                                   { st.d_bursts, v->bursts, C * sizeof(uint64_t) } });
 }
 extern "C" int selenite_rx_get_nb_state(selenite_rx_instance *S, const selenite_rx_nb_state_view *v) { return nb_state_copy(S, v, true); }
 extern "C" int selenite_rx_set_nb_state(selenite_rx_instance *S, const selenite_rx_nb_state_view *v) { return nb_state_copy(S, v, false); }

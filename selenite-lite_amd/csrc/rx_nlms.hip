@@ -220,15 +220,11 @@ int NrStage::init_state(selenite_rx_instance *S)
 {
     if (kind == SELENITE_RX_NR_OFF) return SELENITE_RX_SUCCESS;
     const size_t C = S->cfg.channels, N = taps, D = delay;
-    std::vector<float> w(C * N);
-    for (size_t c = 0; c < C; ++c) std::memcpy(&w[c * N], h_init.data(), N * sizeof(float));
-    HIPCHK(S, hipMemcpyAsync(d_coeffs, w.data(), C * N * sizeof(float), hipMemcpyHostToDevice, S->stream));
     HIPCHK(S, hipMemsetAsync(d_window, 0, C * (N - 1) * sizeof(float), S->stream));
     HIPCHK(S, hipMemsetAsync(d_delay, 0, C * D * sizeof(float), S->stream));
     HIPCHK(S, hipMemsetAsync(d_energy, 0, C * sizeof(float), S->stream));
     HIPCHK(S, hipMemsetAsync(d_x0, 0, C * sizeof(float), S->stream));
-    HIPCHK(S, hipStreamSynchronize(S->stream));      // (w is a host temporary)
-    return SELENITE_RX_SUCCESS;
+    return fill_rows(S, d_coeffs, C, h_init.data(), N);     // (drains the stream)
 }
 
 NrParams NrStage::params(ChanRange r, const RxParams &p) const
@@ -251,10 +247,7 @@ extern "C" int selenite_rx_set_nr(selenite_rx_instance *S, const selenite_rx_nr_
 {
     if (!S) return fail(nullptr, SELENITE_RX_ARGUMENT_ERROR, "selenite_rx_set_nr: S is NULL");
     // everything is validated before anything changes: a refused call leaves the instance as it was
-    if (nr && nr->struct_size != sizeof(selenite_rx_nr_config)) {
-        last_error() = "selenite_rx_set_nr: struct_size is not sizeof(selenite_rx_nr_config)";
-        return SELENITE_RX_ARGUMENT_ERROR;
-    }
+    if (nr && nr->struct_size != sizeof(selenite_rx_nr_config)) return refuse("selenite_rx_set_nr", "struct_size is not sizeof(selenite_rx_nr_config)");
     if (nr && nr->kind != SELENITE_RX_NR_OFF) {
         const uint32_t N = nr->num_taps;
         const char *bad = nullptr;
@@ -265,13 +258,9 @@ extern "C" int selenite_rx_set_nr(selenite_rx_instance *S, const selenite_rx_nr_
         else if (nr->coeffs_init)
             for (uint32_t k = 0; k < N && !bad; ++k)
                 if (!std::isfinite(nr->coeffs_init[k])) bad = "coeffs_init holds a non-finite weight";
-        if (bad) {
-            last_error() = std::string("selenite_rx_set_nr: ") + bad;
-            return SELENITE_RX_ARGUMENT_ERROR;
-        }
+        if (bad) return refuse("selenite_rx_set_nr", bad);
     }
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    if (int rc = drain(S)) return rc;                       // calls in flight still read the old stage
     NrStage &st = S->nr;
     st.release();
     if (!nr || nr->kind == SELENITE_RX_NR_OFF) return SELENITE_RX_SUCCESS;
@@ -295,19 +284,10 @@ extern "C" int selenite_rx_set_nr(selenite_rx_instance *S, const selenite_rx_nr_
 static int nr_state_copy(selenite_rx_instance *S, const selenite_rx_nr_state_view *v, bool to_host)
 {
     if (!S || !v || S->nr.kind == SELENITE_RX_NR_OFF) return SELENITE_RX_ARGUMENT_ERROR;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
     const NrStage &st = S->nr;
-    const size_t C = S->cfg.channels;
-    float *dev[5] = { st.d_coeffs, st.d_window, st.d_delay, st.d_energy, st.d_x0 };
-    float *host[5] = { v->coeffs, v->window, v->delay, v->energy, v->x0 };
-    const size_t n[5] = { C * st.taps, C * (st.taps - 1), C * st.delay, C, C };
-    for (int i = 0; i < 5; ++i) {
-        if (!host[i] || !n[i]) continue;
-        if (to_host) HIPCHK(S, hipMemcpy(host[i], dev[i], n[i] * sizeof(float), hipMemcpyDeviceToHost));
-        else HIPCHK(S, hipMemcpy(dev[i], host[i], n[i] * sizeof(float), hipMemcpyHostToDevice));
-    }
-    return SELENITE_RX_SUCCESS;
+    const size_t b = S->cfg.channels * sizeof(float);       // bytes of one float per channel
+    return copy_rows(S, to_host, { { st.d_coeffs, v->coeffs, b * st.taps }, { st.d_window, v->window, b * (st.taps - 1) }, { st.d_delay, v->delay, b * st.delay },
+                                   { st.d_energy, v->energy, b }, { st.d_x0, v->x0, b } });
 }
 extern "C" int selenite_rx_get_nr_state(selenite_rx_instance *S, const selenite_rx_nr_state_view *v) { return nr_state_copy(S, v, true); }
 extern "C" int selenite_rx_set_nr_state(selenite_rx_instance *S, const selenite_rx_nr_state_view *v) { return nr_state_copy(S, v, false); }

@@ -235,13 +235,9 @@ extern "C" int selenite_rx_set_out(selenite_rx_instance *S, const selenite_rx_ou
         else
             for (uint32_t k = 0; k < out->ni_taps && !bad; ++k)
                 if (!std::isfinite(out->coeffs[k])) bad = "coeffs holds a non-finite tap";
-        if (bad) {
-            last_error() = std::string("selenite_rx_set_out: ") + bad;
-            return code;
-        }
+        if (bad) return refuse("selenite_rx_set_out", bad, code);
     }
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    if (int rc = drain(S)) return rc;                       // calls in flight still read the old stage
     OutStage &st = S->out;
     st.release();
     if (!out) return SELENITE_RX_SUCCESS;
@@ -266,12 +262,7 @@ extern "C" uint32_t selenite_rx_out_values(const selenite_rx_instance *S, uint32
 static int out_state_copy(selenite_rx_instance *S, float *host, bool to_host)
 {
     if (!S || !host || !S->out.on || S->out.taps / S->out.interp < 2) return SELENITE_RX_ARGUMENT_ERROR;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
-    const size_t bytes = (size_t)S->cfg.channels * (S->out.taps / S->out.interp - 1) * sizeof(float);
-    if (to_host) HIPCHK(S, hipMemcpy(host, S->out.d_state, bytes, hipMemcpyDeviceToHost));
-    else HIPCHK(S, hipMemcpy(S->out.d_state, host, bytes, hipMemcpyHostToDevice));
-    return SELENITE_RX_SUCCESS;
+    return copy_rows(S, to_host, { { S->out.d_state, host, (size_t)S->cfg.channels * (S->out.taps / S->out.interp - 1) * sizeof(float) } });
 }
 extern "C" int selenite_rx_get_out_state(selenite_rx_instance *S, float *interp_state) { return out_state_copy(S, interp_state, true); }
 extern "C" int selenite_rx_set_out_state(selenite_rx_instance *S, const float *interp_state)

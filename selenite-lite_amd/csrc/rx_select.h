@@ -127,7 +127,7 @@ inline SelPlan plan_shape(const selenite_rx_config &g, bool delay_is_impulse, bo
 struct SelCall {
     uint32_t block_size = 0; bool q15 = false;      // samples per channel; int16 slots
     bool global_gain = false;    // un-scaled audio wanted: the global gain's two phases finish the call ...
-    bool nr = false;             // ... or the NLMS stage runs on it in front of the AGC
+    bool unscaled_stage = false; // ... or a stage in front of the AGC reads it or runs on it (rx_route.h: StagesOn::any)
     bool hist_ext = false;       // the repair rows exist (allocated, handover repair on)
     bool steps_uniform = false, phase_uniform = false;   // the LO: every channel the same step / the same phase,
     bool steps_grid256 = false;                          // every step a multiple of 2^24 (the fs / 256 grid),
@@ -168,7 +168,7 @@ inline Decision select(const selenite_rx_config &g, const SelPlan &sp, const Sel
     const uint32_t fpass = fused_pass_out(g.block, g.decim), pass16 = split16_pass_out(g.block, g.decim), tq = pass16 * g.decim;
     const uint32_t hs = sp.nds > 0 ? split16_hs(sp.nds, g.decim == 8 ? 4 : (int)g.decim) : 0u;
     uint32_t bs = c.block_size;
-    d.q15 = c.q15 && !(c.global_gain || c.nr);
+    d.q15 = c.q15 && !(c.global_gain || c.unscaled_stage);
     // ---- the cut.  Every call length (a whole number of DSP blocks) runs on the fused kernels (k_ssb_fused: variable-length passes).  One
     // case is better served in two launches: a split-precision instance whose call ends in a partial pass too short for k_ssb_split16 (it
     // wants a whole decimator history in it; only DSP blocks shorter than that history get there): the whole passes are one launch, the
@@ -219,7 +219,7 @@ inline Decision select(const selenite_rx_config &g, const SelPlan &sp, const Sel
         d.repair_all = rerun && am;
         // 16-lane DSP blocks by 4, whole passes, NCO on, neither AM nor FM: the instantiation with the DPP block reductions leaves the
         // block maxima behind, and the envelope reduction folds channels x blocks floats instead of reading the audio again
-        d.env_part = c.global_gain && !c.nr && g.decim == 4 && g.block / g.decim / 4 == 16 && bs / g.decim % 256 == 0 && d.nco_rx && !am && !fm;
+        d.env_part = c.global_gain && !c.unscaled_stage && g.decim == 4 && g.block / g.decim / 4 == 16 && bs / g.decim % 256 == 0 && d.nco_rx && !am && !fm;
     } else if (split && !dec && fpass) {
         // k_hilb_split16: passes of the largest whole number of DSP blocks in 256 (256 itself, or e.g. 192: BASELINE cfg2's literal 48 000
         // samples are 250 blocks of 192), any call length (the last pass may be partial); per-sample NCO.  Every SSB instantiation carries

@@ -309,13 +309,9 @@ extern "C" int selenite_rx_set_spectrum(selenite_rx_instance *S, const selenite_
         else if (sp->window)
             for (uint32_t k = 0; k < sp->fft_len && !bad; ++k)
                 if (!std::isfinite(sp->window[k])) bad = "window holds a non-finite value";
-        if (bad) {
-            last_error() = std::string("selenite_rx_set_spectrum: ") + bad;
-            return code;
-        }
+        if (bad) return refuse("selenite_rx_set_spectrum", bad, code);
     }
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    if (int rc = drain(S)) return rc;                       // calls in flight still read the old stage
     SpecStage &st = S->spec;
     st.release();
     if (!sp) return SELENITE_RX_SUCCESS;
@@ -337,10 +333,8 @@ extern "C" int selenite_rx_set_spectrum(selenite_rx_instance *S, const selenite_
 extern "C" int selenite_rx_get_spectrum(selenite_rx_instance *S, float *rows, uint64_t *frames)
 {
     if (!S || !S->spec.len) return SELENITE_RX_ARGUMENT_ERROR;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
     const SpecStage &st = S->spec;
-    if (rows) HIPCHK(S, hipMemcpy(rows, st.d_rows, (size_t)S->cfg.channels * st.len * sizeof(float), hipMemcpyDeviceToHost));
+    if (int rc = copy_rows(S, true, { { st.d_rows, rows, (size_t)S->cfg.channels * st.len * sizeof(float) } })) return rc;
     // frames transformed since set_spectrum / reset: the complete frames f < pos / N with f % stride == 0
     if (frames) *frames = (st.pos / st.len + st.stride - 1) / st.stride;
     return SELENITE_RX_SUCCESS;
@@ -351,18 +345,12 @@ extern "C" const float *selenite_rx_spectrum_device(const selenite_rx_instance *
 static int spec_state_copy(selenite_rx_instance *S, const selenite_rx_spec_state_view *v, bool to_host)
 {
     if (!S || !v || !S->spec.len) return SELENITE_RX_ARGUMENT_ERROR;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
     SpecStage &st = S->spec;
     const size_t n = (size_t)S->cfg.channels * st.len * sizeof(float);
-    if (to_host) {
-        if (v->rows) HIPCHK(S, hipMemcpy(v->rows, st.d_rows, n, hipMemcpyDeviceToHost));
-        if (v->pending) HIPCHK(S, hipMemcpy(v->pending, st.d_pending, 2 * n, hipMemcpyDeviceToHost));
-        if (v->position) *v->position = st.pos;
-    } else {
-        if (v->rows) HIPCHK(S, hipMemcpy(st.d_rows, v->rows, n, hipMemcpyHostToDevice));
-        if (v->pending) HIPCHK(S, hipMemcpy(st.d_pending, v->pending, 2 * n, hipMemcpyHostToDevice));
-        if (v->position) st.pos = *v->position;
+    if (int rc = copy_rows(S, to_host, { { st.d_rows, v->rows, n }, { st.d_pending, v->pending, 2 * n } })) return rc;
+    if (v->position) {
+        if (to_host) *v->position = st.pos;
+        else st.pos = *v->position;
     }
     return SELENITE_RX_SUCCESS;
 }

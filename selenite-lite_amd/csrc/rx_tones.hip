@@ -248,13 +248,9 @@ extern "C" int selenite_rx_set_tones(selenite_rx_instance *S, const selenite_rx_
         else
             for (size_t i = 0; i < (size_t)f->n_tones * 3; ++i)
                 if (!std::isfinite(f->coeffs[i])) bad = "a coefficient is not finite";
-        if (bad) {
-            last_error() = std::string("selenite_rx_set_tones: ") + bad;
-            return SELENITE_RX_ARGUMENT_ERROR;
-        }
+        if (bad) return refuse("selenite_rx_set_tones", bad);
     }
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));             // calls in flight still read the old stage
+    if (int rc = drain(S)) return rc;                       // calls in flight still read the old stage
     TonesStage &st = S->tones;
     st.release();
     if (!f) return SELENITE_RX_SUCCESS;
@@ -283,19 +279,13 @@ extern "C" int selenite_rx_set_tones(selenite_rx_instance *S, const selenite_rx_
 static int tones_state_copy(selenite_rx_instance *S, const selenite_rx_tones_state_view *v, bool to_host)
 {
     if (!S || !v || !S->tones.on) return SELENITE_RX_ARGUMENT_ERROR;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
     TonesStage &st = S->tones;
     const size_t C = S->cfg.channels, K = st.n_tones;
-    void *const dev[9] = { st.d_s, st.d_energy, st.d_power, st.d_frame_energy, st.d_last_best, st.d_tone, st.d_cand, st.d_run, st.d_changes };
-    void *const host[9] = { v->s, v->energy, v->power, v->frame_energy, v->last_best, v->tone, v->cand, v->run, v->changes };
-    const size_t bytes[9] = { C * K * 2 * sizeof(float), C * sizeof(float), C * K * sizeof(float), C * sizeof(float), C * sizeof(uint32_t),
-                              C * sizeof(uint32_t), C * sizeof(uint32_t), C * sizeof(uint32_t), C * sizeof(uint64_t) };
-    for (int k = 0; k < 9; ++k) {
-        if (!host[k]) continue;
-        if (to_host) HIPCHK(S, hipMemcpy(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost));
-        else HIPCHK(S, hipMemcpy(dev[k], host[k], bytes[k], hipMemcpyHostToDevice));
-    }
+    if (int rc = copy_rows(S, to_host, { { st.d_s, v->s, C * K * 2 * sizeof(float) }, { st.d_energy, v->energy, C * sizeof(float) },
+                                         { st.d_power, v->power, C * K * sizeof(float) }, { st.d_frame_energy, v->frame_energy, C * sizeof(float) },
+                                         { st.d_last_best, v->last_best, C * sizeof(uint32_t) }, { st.d_tone, v->tone, C * sizeof(uint32_t) },
+                                         { st.d_cand, v->cand, C * sizeof(uint32_t) }, { st.d_run, v->run, C * sizeof(uint32_t) },
+                                         { st.d_changes, v->changes, C * sizeof(uint64_t) } })) return rc;
     if (v->position) {
         if (to_host) *v->position = st.pos;
         else st.pos = *v->position;
@@ -308,12 +298,9 @@ extern "C" int selenite_rx_set_tones_state(selenite_rx_instance *S, const seleni
 extern "C" int selenite_rx_get_tones(selenite_rx_instance *S, uint32_t *tone, float *power, uint64_t *frames)
 {
     if (!S || !S->tones.on) return SELENITE_RX_ARGUMENT_ERROR;
-    HIPCHK(S, hipSetDevice(S->device));
-    HIPCHK(S, hipStreamSynchronize(S->stream));
     const TonesStage &st = S->tones;
     const size_t C = S->cfg.channels;
-    if (tone) HIPCHK(S, hipMemcpy(tone, st.d_tone, C * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (power) HIPCHK(S, hipMemcpy(power, st.d_power, C * st.n_tones * sizeof(float), hipMemcpyDeviceToHost));
+    if (int rc = copy_rows(S, true, { { st.d_tone, tone, C * sizeof(uint32_t) }, { st.d_power, power, C * st.n_tones * sizeof(float) } })) return rc;
     if (frames) *frames = st.pos / st.frame_blocks;
     return SELENITE_RX_SUCCESS;
 }

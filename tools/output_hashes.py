@@ -4,7 +4,12 @@ of shapes, arithmetics and slot formats on seeded input: run it with two builds 
 not meant to change a bit did not (`SELENITE_RX_LIB=old.so python3 tools/output_hashes.py > a; python3 tools/output_hashes.py > b; diff a b`).
 The stage rows behind them (NLMS, output stage, spectrum tap: each alone and all three, f32 and int16 slots, device calls and host-pointer
 calls cut into 1 MiB channel chunks) hash the audio, the chain state and the stages' state; they run in a child process, because the library
-reads SELENITE_RX_HOST_CHUNK_MB once (`--stage-rows` alone: only those, in this process).  Between the two, the edge rows: calls at the
+reads SELENITE_RX_HOST_CHUNK_MB once (`--stage-rows` alone: only those, in this process).  Behind them, in the same child, the route rows:
+the other five stages (noise blanker, I/Q correction, meter with gate, audio filter, tone detector), each alone and all eight together, at
+130 channels (cfg3: chunks of 64 + 64 + 2) on six chains -- cfg3 in `auto` and `cmsis` with calls of 4096 + 256 samples, cfg3 with DSP blocks of
+128 samples in `split16` and `auto` with calls of 4096 + 128 (the call the dispatcher cuts in two), cfg1 in `fma` with 768, a CW chain --
+f32 and int16 slots, the device call, the host-pointer call, and with a global gain the host-pointer call and the two-phase device entries
+(not with an output stage); audio + chain state + every stage's state.  Between the chain rows and these, the edge rows: calls at the
 edges of the rule that picks the kernel of a call (csrc/rx_select.h) -- short calls, partial passes, cut calls, the AUTO forms, FM, the
 dense flavour, the five LO situations, global gain, NLMS, the repair switched off, the generic path -- 33 channels, three calls each, with
 the kernel name, the NCO path and the form of the last AUTO launch beside the hash (`--chain-rows`: these and the chain rows, no child)."""
@@ -63,6 +68,71 @@ def stage_rows():
                         h.update(np.ascontiguousarray(st[k]).tobytes())
                 print("stages", stages, "q15" if q15 else "f32", "host-chunked" if host else "device", rx.kernel_name(), h.hexdigest()[:24])
                 rx.close(); d_in.free(); d_out.free()
+
+
+def route_rows():
+    """every stage in front of and behind the AGC on every route of the dispatcher (csrc/rx_route.h), three calls each"""
+    n = 130
+    own = (np.arange(n, dtype=np.uint64) * 0x9E3779B1 % (1 << 32)).astype(np.uint32)
+
+    def b128(arith, **kw):
+        return ch.ChainSpec(n, 128, 4, 256, 63, 0, sr.MODE_USB, arith, nco=True, **kw)
+
+    chains = [("cfg3 auto", lambda **kw: ch.baseline_spec("cfg3", n, sr.ARITH_AUTO, nco_steps=own, **kw), 4096 + 256),
+              ("cfg3 cmsis", lambda **kw: ch.baseline_spec("cfg3", n, sr.ARITH_CMSIS, **kw), 4096 + 256),
+              ("cfg3-b128 split16", lambda **kw: b128(sr.ARITH_SPLIT16, nco_step_all=GRID, **kw), 4096 + 128),
+              ("cfg3-b128 auto", lambda **kw: b128(sr.ARITH_AUTO, nco_steps=own, **kw), 4096 + 128),
+              ("cfg1 fma", lambda **kw: ch.baseline_spec("cfg1", n, sr.ARITH_FMA, **kw), 768),
+              ("cfg4 cw", lambda **kw: ch.baseline_spec("cfg4", n, sr.ARITH_CMSIS, **kw), 1024)]
+    interp = sr.design_interp(32, 4, 0.1)
+    sections = np.stack([sr.design_biquad(sr.BIQUAD_NOTCH, 0.05, 8.0), sr.design_biquad(sr.BIQUAD_PEAKING, 0.11, 2.0, 6.0), sr.design_deemphasis(6.0)])
+    tones = sr.design_tones(np.linspace(0.01, 0.2, 16))
+    setups = dict(nb=lambda rx: rx.set_nb(frame=64, guard=2, max_hits=8, threshold=4.0, alpha=0.125, clamp=2.0),
+                  iqc=lambda rx: rx.set_iqc(frame=64),
+                  meter=lambda rx: rx.set_meter(sr.SQ_ABOVE, gate=1, hang=1, attack=0.5, decay=0.9375, open_level=2e-2, close_level=4e-3),
+                  afilt=lambda rx: rx.set_afilt(sections),
+                  tones=lambda rx: rx.set_tones(tones, frame_blocks=3, confirm=2, release=2, ratio=0.1),
+                  nr=lambda rx: rx.set_nr(sr.NR_DENOISE, num_taps=16, delay=8, mu=0.05),
+                  out=lambda rx: rx.set_out(4, interp, sr.OUT_STEREO),
+                  spec=lambda rx: rx.set_spectrum(64, 1, 1, 0.25))
+    states = dict(nb=lambda rx: rx.nb_state(), iqc=lambda rx: rx.iqc_state(), meter=lambda rx: rx.meter_state(), afilt=lambda rx: rx.afilt_state(),
+                  tones=lambda rx: rx.tones_state(), nr=lambda rx: rx.nr_state(), out=lambda rx: dict(interp=rx.out_state()),
+                  spec=lambda rx: rx.spectrum_state())
+    for label, mk, bs in chains:
+        for stages in ("nb", "iqc", "meter", "afilt", "tones", "spec+iqc+nb+tones+afilt+nr+meter+out"):
+            on = stages.split("+")
+            for slot, entry in (("f32", "device"), ("f32", "host-chunked"), ("q15", "device"), ("q15", "host-chunked"), ("f32", "global-host"), ("f32", "global-split")):
+                if entry == "global-split" and "out" in on:
+                    continue                      # the split calls exchange audio at the decimated rate: refused with an output stage
+                q15, glob = slot == "q15", entry.startswith("global")
+                rx = sr.Rx(mk(agc_global=True).config() if glob else mk().config())
+                for k in on:
+                    setups[k](rx)
+                dt = np.int16 if q15 else np.float32
+                vals, nblk = rx.out_values(bs), bs // rx.cfg.block
+                d_in, d_out, d_env = sr.DeviceBuffer(n * bs * 2 * np.dtype(dt).itemsize), sr.DeviceBuffer(n * vals * np.dtype(dt).itemsize), sr.DeviceBuffer(4 * nblk)
+                h = hashlib.sha256()
+                for call in range(3):
+                    data = sr.synth_iq_host(0, n, call * bs, bs, ch.SEED)
+                    if q15:
+                        data = np.clip(np.trunc(data * 32768.0), -32768, 32767).astype(np.int16)
+                    if entry in ("host-chunked", "global-host"):
+                        y = (rx.process_q15 if q15 else rx.process)(data)
+                    else:
+                        d_in.upload(data)
+                        if entry == "global-split":
+                            rx.global_phase1(d_in.ptr, d_out.ptr, d_env.ptr, bs)
+                            rx.global_phase2(d_out.ptr, d_env.ptr, bs)
+                        else:
+                            (rx.process_q15_device if q15 else rx.process_device)(d_in.ptr, d_out.ptr, bs)
+                        rx.sync()
+                        y = d_out.download((n, vals), dt)
+                    h.update(np.ascontiguousarray(y).tobytes())
+                for st in [rx.state()] + [states[k](rx) for k in on]:
+                    for k in sorted(st):
+                        h.update(np.ascontiguousarray(st[k]).tobytes())
+                print("route", label, bs, stages, slot, entry, rx.kernel_name(), h.hexdigest()[:24])
+                rx.close(); d_in.free(); d_out.free(); d_env.free()
 
 
 SHAPES = [("cfg1", 256 * 4), ("cfg2", 256 * 5), ("cfg2_48k128", 128 * 7), ("cfg2_48k", 192 * 5), ("cfg3", 1024 * 3), ("cfg3_by8", 2048), ("cfg4", 256 * 4)]
@@ -186,6 +256,7 @@ def edge_rows():
 def main():
     if sys.argv[1:] == ["--stage-rows"]:
         stage_rows()
+        route_rows()
         return 0
     chain_rows()
     edge_rows()
