@@ -229,8 +229,7 @@ struct __attribute__((visibility("hidden"))) SpecStage {
     // one launch on the instance's stream, on the caller's own input (f32, or int16 read directly)
     int run(selenite_rx_instance *S, ChanRange r, uint64_t at, const void *src, bool src_q15, uint32_t block_size) const;
 };
-// host: twiddleCoef_n regenerated, tw[n][2] = (cos, sin)(2 pi i / n) as the reference's table holds them
-void spec_twiddles(float *tw, uint32_t n);
+// (host: spec_twiddles, twiddleCoef_n regenerated as the reference's table holds it, lives in rx_fft8.h)
 
 // ---- impulse noise blanker (rx_nb.hip): frame power -> arm_mean_f32 -> level, hits over threshold * level blanked, on the raw input ----
 struct NbParams {

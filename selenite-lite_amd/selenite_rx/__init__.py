@@ -214,6 +214,27 @@ RING_ABI_SYMBOLS = [
     "selenite_ring_get_state", "selenite_ring_set_state", "selenite_ring_time_device",
 ]
 
+
+class ChanConfig(C.Structure):
+    """struct selenite_chan_config (include/selenite_chan.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("bands", C.c_uint32), ("fft_len", C.c_uint32), ("oversample", C.c_uint32),
+                ("taps_per_branch", C.c_uint32), ("n_bins", C.c_uint32), ("reserved", C.c_uint32),
+                ("coeffs", f32p), ("bins", u32p)]
+
+
+class ChanStateView(C.Structure):
+    """struct selenite_chan_state_view."""
+    _fields_ = [("history", f32p), ("position", u64p)]
+
+
+# every symbol include/selenite_chan.h declares
+CHAN_ABI_SYMBOLS = [
+    "selenite_chan_init", "selenite_chan_free", "selenite_chan_status", "selenite_chan_error_string",
+    "selenite_chan_set_stream", "selenite_chan_sync", "selenite_chan_reset", "selenite_chan_get_state", "selenite_chan_set_state",
+    "selenite_chan_out_channels", "selenite_chan_out_len",
+    "selenite_chan_process_f32_device", "selenite_chan_process_q15_device", "selenite_chan_design_prototype",
+]
+
 _lib = None
 
 
@@ -347,6 +368,27 @@ def lib():
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
+        if hasattr(L, "selenite_chan_init"):                # (an older build named by SELENITE_RX_LIB lacks the channeliser)
+            L.selenite_chan_init.argtypes = [C.POINTER(vp), C.POINTER(ChanConfig)]
+            L.selenite_chan_free.argtypes = [vp]
+            L.selenite_chan_free.restype = None
+            L.selenite_chan_status.argtypes = [vp]
+            L.selenite_chan_error_string.argtypes = [vp]
+            L.selenite_chan_error_string.restype = C.c_char_p
+            L.selenite_chan_set_stream.argtypes = [vp, vp]
+            L.selenite_chan_sync.argtypes = [vp]
+            L.selenite_chan_reset.argtypes = [vp]
+            L.selenite_chan_get_state.argtypes = [vp, C.POINTER(ChanStateView)]
+            L.selenite_chan_set_state.argtypes = [vp, C.POINTER(ChanStateView)]
+            L.selenite_chan_out_channels.argtypes = [vp]
+            L.selenite_chan_out_channels.restype = C.c_uint32
+            L.selenite_chan_out_len.argtypes = [vp, C.c_uint32]
+            L.selenite_chan_out_len.restype = C.c_uint32
+            L.selenite_chan_process_f32_device.argtypes = [vp, vp, vp, C.c_uint32]
+            L.selenite_chan_process_f32_device.restype = None
+            L.selenite_chan_process_q15_device.argtypes = [vp, vp, vp, C.c_uint32]
+            L.selenite_chan_process_q15_device.restype = None
+            L.selenite_chan_design_prototype.argtypes = [f32p, C.c_uint32, C.c_uint32, C.c_double]
         _lib = L
     return _lib
 
@@ -1422,6 +1464,99 @@ class Tx:
     def close(self):
         if self.h:
             self.L.selenite_tx_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def design_chan_prototype(fft_len, taps_per_branch, width=1.0):
+    """the channeliser's prototype g[K P] in CMSIS order: design_lowpass(K P, 0.5 * width / K), width in channel spacings (0 < width <= 2)"""
+    g = np.empty(fft_len * taps_per_branch, np.float32)
+    rc = lib().selenite_chan_design_prototype(_fp(g), fft_len, taps_per_branch, float(width))
+    if rc:
+        raise ValueError("selenite_chan_design_prototype: %d" % rc)
+    return g
+
+
+class Channelizer:
+    """One selenite_chan object (include/selenite_chan.h): `bands` wideband I/Q streams in, bands * n_bins channels out, in the layout
+    Rx.process_device reads.  Device pointers only (DeviceBuffer.ptr)."""
+
+    def __init__(self, bands, fft_len, oversample, taps_per_branch, coeffs, bins=None):
+        self.L = lib()
+        coeffs = np.ascontiguousarray(coeffs, np.float32)
+        assert coeffs.size == fft_len * taps_per_branch, coeffs.shape
+        b = None if bins is None else np.ascontiguousarray(bins, np.uint32)
+        self.bands, self.fft_len, self.oversample, self.taps_per_branch = int(bands), int(fft_len), int(oversample), int(taps_per_branch)
+        self.n_bins = self.fft_len if b is None else int(b.size)
+        cfg = ChanConfig(C.sizeof(ChanConfig), self.bands, self.fft_len, self.oversample, self.taps_per_branch, self.n_bins, 0, _fp(coeffs),
+                         None if b is None else b.ctypes.data_as(u32p))
+        self.h = C.c_void_p()
+        rc = self.L.selenite_chan_init(C.byref(self.h), C.byref(cfg))
+        if rc:
+            raise RxError(rc, "selenite_chan_init failed (no GPU, or a bad configuration)")
+        self.decim = self.fft_len // self.oversample
+        self.hist_len = self.fft_len * self.taps_per_branch - self.decim
+
+    def status(self):
+        return self.L.selenite_chan_status(self.h)
+
+    def check(self):
+        rc = self.L.selenite_chan_status(self.h)
+        if rc:
+            raise RxError(rc, self.L.selenite_chan_error_string(self.h).decode())
+
+    def out_channels(self):
+        return self.L.selenite_chan_out_channels(self.h)
+
+    def out_len(self, block_size):
+        return self.L.selenite_chan_out_len(self.h, block_size)
+
+    def process_device(self, d_src, d_dst, block_size):
+        """d_src [bands][block_size][2] f32 -> d_dst [bands * n_bins][block_size / D][2] f32, asynchronous; a refused call raises"""
+        self.L.selenite_chan_process_f32_device(self.h, d_src, d_dst, block_size)
+        self.check()
+
+    def process_q15_device(self, d_src, d_dst, block_size):
+        """int16 input (arm_q15_to_float), f32 output"""
+        self.L.selenite_chan_process_q15_device(self.h, d_src, d_dst, block_size)
+        self.check()
+
+    def set_stream(self, stream_ptr):
+        return self.L.selenite_chan_set_stream(self.h, stream_ptr)
+
+    def sync(self):
+        rc = self.L.selenite_chan_sync(self.h)
+        if rc:
+            raise RxError(rc, self.L.selenite_chan_error_string(self.h).decode())
+
+    def reset(self):
+        return self.L.selenite_chan_reset(self.h)
+
+    def state(self):
+        a = {"history": np.zeros((self.bands, self.hist_len, 2), np.float32), "position": np.zeros(1, np.uint64)}
+        v = ChanStateView(_fp(a["history"]), a["position"].ctypes.data_as(u64p))
+        rc = self.L.selenite_chan_get_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, self.L.selenite_chan_error_string(self.h).decode())
+        return a
+
+    def set_state(self, a):
+        hist = np.ascontiguousarray(a["history"], np.float32) if a.get("history") is not None else None
+        pos = np.ascontiguousarray(a["position"], np.uint64) if a.get("position") is not None else None
+        assert hist is None or hist.shape == (self.bands, self.hist_len, 2), hist.shape
+        v = ChanStateView(None if hist is None else _fp(hist), None if pos is None else pos.ctypes.data_as(u64p))
+        rc = self.L.selenite_chan_set_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, self.L.selenite_chan_error_string(self.h).decode())
+
+    def close(self):
+        if self.h:
+            self.L.selenite_chan_free(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
