@@ -290,6 +290,18 @@ constexpr int kZIMG = (kZN + 8 + 7) & ~7;                          // halfs per 
 constexpr int oZ16 = oHQ + kHLen, oZF = oZ16 + 2 * kZIMG;          // 4 images of kZIMG halfs = 2 kZIMG floats
 constexpr int kTotal16 = oZF + 2 * kPass;                          // + the pass's interpolator input in f32, both rails
 
+// cmul<0> (rx_device.h) for the up-mix of k_tx_split16, same bits, with the four products kept apart as plain f32 registers.  Left to
+// itself the compiler packs the products and sums of two outputs into v_pk_mul_f32 / v_pk_add_f32 with operand halves picked by op_sel;
+// with two waves on a SIMD -- this kernel's matrix passes beside another workgroup's up-mix, i.e. a batch larger than one workgroup per SIMD
+// -- a few channels per call came out with the first product alone in I of the second output of a store, lanes 48 to 63
+// (tests/test_gpu_tx_handover.py, profiles/tx_handover/README.md).  The empty asm is no instruction: it only hides the values from the packing.
+__device__ __forceinline__ float2 cmul_np(float2 A, float2 B)
+{
+    float ac = A.x * B.x, bd = A.y * B.y, ad = A.x * B.y, bc = A.y * B.x;
+    asm volatile("" : "+v"(ac), "+v"(bd), "+v"(ad), "+v"(bc));
+    return make_float2(ac - bd, ad + bc);
+}
+
 template <int NCO, typename TIn, typename TOut>
 __global__ __launch_bounds__(64, 2) void k_tx_split16(TxParams p, uint32_t delay_idx, const float2 *__restrict__ lo,
                                                       const void *__restrict__ ttab16, int tap_sc,
@@ -500,18 +512,18 @@ __global__ __launch_bounds__(64, 2) void k_tx_split16(TxParams p, uint32_t delay
                 float2 y0 = make_float2(t.x, t.y), y1 = make_float2(t.z, t.w);
                 if constexpr (NCO == 2) {
                     const float4 l = *reinterpret_cast<const float4 *>(lo + (size_t)pass * kPass * kL + o);
-                    y0 = cmul<0>(y0, make_float2(l.x, -l.y));
-                    y1 = cmul<0>(y1, make_float2(l.z, -l.w));
+                    y0 = cmul_np(y0, make_float2(l.x, -l.y));
+                    y1 = cmul_np(y1, make_float2(l.z, -l.w));
                 } else if constexpr (NCO == 3) {                          // periodic shared LO: o mod 256 = 128 (j & 1) + 2 lane
                     const float4 l = lo_per[j & 1];
-                    y0 = cmul<0>(y0, make_float2(l.x, -l.y));
-                    y1 = cmul<0>(y1, make_float2(l.z, -l.w));
+                    y0 = cmul_np(y0, make_float2(l.x, -l.y));
+                    y1 = cmul_np(y1, make_float2(l.z, -l.w));
                 } else if constexpr (NCO == 1) {
                     const uint32_t phase = ph0 + (pass * kPass * kL + o) * step;
                     lo_v2f la, lb;                                        // (cos, -sin) pairs, arm_sin/cos_f32 restated (rx_device.h): same bits
                     nco_lo_pair(tab, phase, phase + step, la, lb);
-                    y0 = cmul<0>(y0, make_float2(la.x, -la.y));
-                    y1 = cmul<0>(y1, make_float2(lb.x, -lb.y));
+                    y0 = cmul_np(y0, make_float2(la.x, -la.y));
+                    y1 = cmul_np(y1, make_float2(lb.x, -lb.y));
                 }
                 const size_t at = out_base + (size_t)pass * kPass * kL + o;
                 if constexpr (sizeof(TOut) == 4) {
