@@ -43,9 +43,13 @@ extern "C" {
 
 typedef struct selenite_chan selenite_chan;
 
+/* The most bands one object takes: a band is a workgroup of 64 threads in the main kernel's grid x, and a launch holds fewer than 2^32
+ * threads per dimension.  (Memory ends far sooner: the two history buffers of that many bands are 200 GB at K = 64, P = 4.) */
+#define SELENITE_CHAN_MAX_BANDS 0x3FFFFFFu
+
 typedef struct {
     uint32_t struct_size;      /* sizeof(selenite_chan_config): the struct's own growth path */
-    uint32_t bands;            /* wideband streams, >= 1 */
+    uint32_t bands;            /* wideband streams, 1 .. SELENITE_CHAN_MAX_BANDS, and bands * n_bins < 2^32 */
     uint32_t fft_len;          /* K: 64 or 512 (the pure radix-8 lengths of arm_cfft_f32) */
     uint32_t oversample;       /* 1: critically sampled (D = K); 2: D = K / 2, adjacent channels overlap */
     uint32_t taps_per_branch;  /* P: 4, 8, 12 or 16 */

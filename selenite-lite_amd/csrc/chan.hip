@@ -226,12 +226,12 @@ __global__ __launch_bounds__(64) void k_chan(ChanParams q, const TIn *__restrict
     }
 }
 
-// the history behind the call: the newest H samples of (old history, call), into the other buffer
+// the history behind the call: the newest H samples of (old history, call), into the other buffer; blockIdx.y counts the bands from b0
 template <typename TIn>
 __global__ __launch_bounds__(256) void k_chan_hist(const TIn *__restrict__ src, const float *__restrict__ old, float *__restrict__ neu,
-                                                   uint32_t H, uint32_t block_size)
+                                                   uint32_t H, uint32_t block_size, uint32_t b0)
 {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x, b = blockIdx.y;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, b = b0 + blockIdx.y;
     if (i >= H) return;
     const int64_t j = (int64_t)i + block_size;
     const float2 v = j < (int64_t)H ? reinterpret_cast<const float2 *>(old)[(int64_t)b * H + j]
@@ -295,8 +295,12 @@ int process(selenite_chan *Ch, const TIn *src, float *dst, uint32_t block_size, 
     else launch_k<64, TIn>(Ch->P, Ch->ovs, dim3((Ch->bands + 7u) / 8u, runs), Ch->stream, q, src);
     CCHK(Ch, hipGetLastError());
     const uint32_t H = (uint32_t)Ch->H();
-    hipLaunchKernelGGL((k_chan_hist<TIn>), dim3((H + 255u) / 256u, Ch->bands), dim3(256), 0, Ch->stream, src, Ch->d_hist[Ch->cur],
-                       Ch->d_hist[1 - Ch->cur], H, block_size);
+    // gridDim.y is limited to 65535: loop over band slabs (as launch_synth does over channels)
+    for (uint32_t b0 = 0; b0 < Ch->bands; b0 += 32768u) {
+        const uint32_t n = Ch->bands - b0 < 32768u ? Ch->bands - b0 : 32768u;
+        hipLaunchKernelGGL((k_chan_hist<TIn>), dim3((H + 255u) / 256u, n), dim3(256), 0, Ch->stream, src, Ch->d_hist[Ch->cur],
+                           Ch->d_hist[1 - Ch->cur], H, block_size, b0);
+    }
     CCHK(Ch, hipGetLastError());
     Ch->cur = 1 - Ch->cur;
     Ch->position += block_size;
@@ -328,6 +332,7 @@ extern "C" int selenite_chan_init(selenite_chan **out, const selenite_chan_confi
     if (cfg->bands == 0 || (cfg->oversample != 1 && cfg->oversample != 2) || (P != 4 && P != 8 && P != 12 && P != 16) ||
         cfg->n_bins == 0 || cfg->reserved != 0 || !cfg->coeffs)
         return SELENITE_RX_ARGUMENT_ERROR;
+    if (cfg->bands > SELENITE_CHAN_MAX_BANDS) return SELENITE_RX_ARGUMENT_ERROR;        // (the bands are k_chan's grid x: 64 threads each, under 2^32)
     if ((uint64_t)cfg->bands * cfg->n_bins > 0xFFFFFFFFull) return SELENITE_RX_ARGUMENT_ERROR;
     if (!cfg->bins && cfg->n_bins != K) return SELENITE_RX_ARGUMENT_ERROR;
     for (uint32_t i = 0; i < K * P; ++i)

@@ -77,7 +77,9 @@ def init(cfg):
     return rc_, h
 
 
-BAD = [("struct_size", 8, sr.ARGUMENT_ERROR), ("bands", 0, sr.ARGUMENT_ERROR), ("fft_len", 128, sr.LENGTH_ERROR), ("fft_len", 0, sr.LENGTH_ERROR),
+BAD = [("struct_size", 8, sr.ARGUMENT_ERROR), ("bands", 0, sr.ARGUMENT_ERROR),
+       ("bands", 1 << 26, sr.ARGUMENT_ERROR),                    # SELENITE_CHAN_MAX_BANDS + 1 (bands * n_bins = 3 * 2^26 is still below 2^32)
+       ("fft_len", 128, sr.LENGTH_ERROR), ("fft_len", 0, sr.LENGTH_ERROR),
        ("oversample", 0, sr.ARGUMENT_ERROR), ("oversample", 4, sr.ARGUMENT_ERROR), ("taps_per_branch", 6, sr.ARGUMENT_ERROR),
        ("taps_per_branch", 20, sr.ARGUMENT_ERROR), ("n_bins", 0, sr.ARGUMENT_ERROR), ("reserved", 1, sr.ARGUMENT_ERROR)]
 

@@ -1,6 +1,8 @@
 """GPU: the polyphase channeliser (include/selenite_chan.h, csrc/chan.hip) against the numpy restatement (tests/chan_oracle.py, pinned to
 the reference's arm_dot_prod_f32 + arm_cfft_f32 by tests/test_chan_oracle.py): outputs, history and position as bits; where the restatement
-is not finite, the same NaN / Inf positions.  Every compiled k_chan<K, P, OVS, TIn> runs at least once."""
+is not finite, the same NaN / Inf positions.  Every compiled k_chan<K, P, OVS, TIn> runs at least once: the 16 (K, P, OVS) in
+test_every_instantiation_f32 and again in test_int16_input.  Band counts past the first workgroup, the tile and run edges, state on either
+buffer and the headline geometry are in tests/test_gpu_chan_scale.py."""
 import ctypes as C
 import os
 
@@ -109,15 +111,24 @@ def test_every_instantiation_f32(k, p, ovs):
     pr.close()
 
 
-@pytest.mark.parametrize("k,ovs,p", [(64, 1, 12), (64, 2, 8), (512, 1, 16), (512, 2, 4)])
-def test_int16_input(k, ovs, p):
-    bands = 3 if k == 64 else 2
+def int16_case(bands, k, ovs, p):
     pr = Pair(bands, k, ovs, p)
     x = stream(bands, 37 * (k // ovs), 12, q15=True)
     x[0, 5], x[bands - 1, -1] = (-32768, 32767), (-32768, -32768)
     pr.call(x[:, :20 * (k // ovs)], "first")
     pr.call(x[:, 20 * (k // ovs):], "second")                   # (the history holds converted samples)
     pr.close()
+
+
+@pytest.mark.parametrize("k,ovs,p", [(k, ovs, p) for k in KS for ovs in OVS for p in PS])
+def test_int16_input(k, ovs, p):
+    """every k_chan<K, P, OVS, int16_t>: two full-scale samples, two calls"""
+    int16_case(3 if k == 64 else 2, k, ovs, p)
+
+
+def test_int16_input_nine_bands():
+    """K 64: a full wave of eight bands and a second workgroup with one live slot"""
+    int16_case(9, 64, 2, 12)
 
 
 @pytest.mark.parametrize("ovs", OVS)
