@@ -235,6 +235,26 @@ CHAN_ABI_SYMBOLS = [
     "selenite_chan_process_f32_device", "selenite_chan_process_q15_device", "selenite_chan_design_prototype",
 ]
 
+class CombConfig(C.Structure):
+    """struct selenite_comb_config (include/selenite_comb.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("bands", C.c_uint32), ("fft_len", C.c_uint32), ("oversample", C.c_uint32),
+                ("taps_per_branch", C.c_uint32), ("n_bins", C.c_uint32), ("q15_rounding", C.c_uint32), ("reserved", C.c_uint32),
+                ("coeffs", f32p), ("bins", u32p)]
+
+
+class CombStateView(C.Structure):
+    """struct selenite_comb_state_view."""
+    _fields_ = [("history", f32p), ("position", u64p)]
+
+
+# every symbol include/selenite_comb.h declares
+COMB_ABI_SYMBOLS = [
+    "selenite_comb_init", "selenite_comb_free", "selenite_comb_status", "selenite_comb_error_string",
+    "selenite_comb_set_stream", "selenite_comb_sync", "selenite_comb_reset", "selenite_comb_get_state", "selenite_comb_set_state",
+    "selenite_comb_in_channels", "selenite_comb_out_len",
+    "selenite_comb_process_f32_device", "selenite_comb_process_q15_device", "selenite_comb_design_prototype",
+]
+
 _lib = None
 
 
@@ -389,6 +409,27 @@ def lib():
             L.selenite_chan_process_q15_device.argtypes = [vp, vp, vp, C.c_uint32]
             L.selenite_chan_process_q15_device.restype = None
             L.selenite_chan_design_prototype.argtypes = [f32p, C.c_uint32, C.c_uint32, C.c_double]
+        if hasattr(L, "selenite_comb_init"):                # (an older build named by SELENITE_RX_LIB lacks the combiner)
+            L.selenite_comb_init.argtypes = [C.POINTER(vp), C.POINTER(CombConfig)]
+            L.selenite_comb_free.argtypes = [vp]
+            L.selenite_comb_free.restype = None
+            L.selenite_comb_status.argtypes = [vp]
+            L.selenite_comb_error_string.argtypes = [vp]
+            L.selenite_comb_error_string.restype = C.c_char_p
+            L.selenite_comb_set_stream.argtypes = [vp, vp]
+            L.selenite_comb_sync.argtypes = [vp]
+            L.selenite_comb_reset.argtypes = [vp]
+            L.selenite_comb_get_state.argtypes = [vp, C.POINTER(CombStateView)]
+            L.selenite_comb_set_state.argtypes = [vp, C.POINTER(CombStateView)]
+            L.selenite_comb_in_channels.argtypes = [vp]
+            L.selenite_comb_in_channels.restype = C.c_uint32
+            L.selenite_comb_out_len.argtypes = [vp, C.c_uint32]
+            L.selenite_comb_out_len.restype = C.c_uint32
+            L.selenite_comb_process_f32_device.argtypes = [vp, vp, vp, C.c_uint32]
+            L.selenite_comb_process_f32_device.restype = None
+            L.selenite_comb_process_q15_device.argtypes = [vp, vp, vp, C.c_uint32]
+            L.selenite_comb_process_q15_device.restype = None
+            L.selenite_comb_design_prototype.argtypes = [f32p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint32]
         _lib = L
     return _lib
 
@@ -1557,6 +1598,100 @@ class Channelizer:
     def close(self):
         if self.h:
             self.L.selenite_chan_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def design_comb_prototype(fft_len, taps_per_branch, width=1.0, oversample=1):
+    """the combiner's prototype g[K P] in CMSIS order: design_chan_prototype(K, P, width) times K * D, D = K / oversample, so that a constant
+    on channel 0 leaves as that constant (the 1 / K is arm_cfft_f32's own)"""
+    g = np.empty(fft_len * taps_per_branch, np.float32)
+    rc = lib().selenite_comb_design_prototype(_fp(g), fft_len, taps_per_branch, float(width), oversample)
+    if rc:
+        raise ValueError("selenite_comb_design_prototype: %d" % rc)
+    return g
+
+
+class Combiner:
+    """One selenite_comb object (include/selenite_comb.h): bands * n_bins TX channel rows in, in the layout Tx.process_device writes, `bands`
+    wideband I/Q streams out, f32 or int16.  Device pointers only (DeviceBuffer.ptr)."""
+
+    def __init__(self, bands, fft_len, oversample, taps_per_branch, coeffs, bins=None, q15_rounding=0):
+        self.L = lib()
+        coeffs = np.ascontiguousarray(coeffs, np.float32)
+        assert coeffs.size == fft_len * taps_per_branch, coeffs.shape
+        b = None if bins is None else np.ascontiguousarray(bins, np.uint32)
+        self.bands, self.fft_len, self.oversample, self.taps_per_branch = int(bands), int(fft_len), int(oversample), int(taps_per_branch)
+        self.n_bins = self.fft_len if b is None else int(b.size)
+        cfg = CombConfig(C.sizeof(CombConfig), self.bands, self.fft_len, self.oversample, self.taps_per_branch, self.n_bins, int(q15_rounding), 0,
+                         _fp(coeffs), None if b is None else b.ctypes.data_as(u32p))
+        self.h = C.c_void_p()
+        rc = self.L.selenite_comb_init(C.byref(self.h), C.byref(cfg))
+        if rc:
+            raise RxError(rc, "selenite_comb_init failed (no GPU, or a bad configuration)")
+        self.interp = self.fft_len // self.oversample
+        self.hist_len = self.taps_per_branch * self.oversample - 1
+
+    def status(self):
+        return self.L.selenite_comb_status(self.h)
+
+    def check(self):
+        rc = self.L.selenite_comb_status(self.h)
+        if rc:
+            raise RxError(rc, self.L.selenite_comb_error_string(self.h).decode())
+
+    def in_channels(self):
+        return self.L.selenite_comb_in_channels(self.h)
+
+    def out_len(self, block_size):
+        return self.L.selenite_comb_out_len(self.h, block_size)
+
+    def process_device(self, d_src, d_dst, block_size):
+        """d_src [bands * n_bins][block_size][2] f32 -> d_dst [bands][block_size * D][2] f32, asynchronous; a refused call raises"""
+        self.L.selenite_comb_process_f32_device(self.h, d_src, d_dst, block_size)
+        self.check()
+
+    def process_q15_device(self, d_src, d_dst, block_size):
+        """f32 input, int16 output (arm_float_to_q15, saturating)"""
+        self.L.selenite_comb_process_q15_device(self.h, d_src, d_dst, block_size)
+        self.check()
+
+    def set_stream(self, stream_ptr):
+        return self.L.selenite_comb_set_stream(self.h, stream_ptr)
+
+    def sync(self):
+        rc = self.L.selenite_comb_sync(self.h)
+        if rc:
+            raise RxError(rc, self.L.selenite_comb_error_string(self.h).decode())
+
+    def reset(self):
+        return self.L.selenite_comb_reset(self.h)
+
+    def state(self):
+        a = {"history": np.zeros((self.bands * self.n_bins, self.hist_len, 2), np.float32), "position": np.zeros(1, np.uint64)}
+        v = CombStateView(_fp(a["history"]), a["position"].ctypes.data_as(u64p))
+        rc = self.L.selenite_comb_get_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, self.L.selenite_comb_error_string(self.h).decode())
+        return a
+
+    def set_state(self, a):
+        hist = np.ascontiguousarray(a["history"], np.float32) if a.get("history") is not None else None
+        pos = np.ascontiguousarray(a["position"], np.uint64) if a.get("position") is not None else None
+        assert hist is None or hist.shape == (self.bands * self.n_bins, self.hist_len, 2), hist.shape
+        v = CombStateView(None if hist is None else _fp(hist), None if pos is None else pos.ctypes.data_as(u64p))
+        rc = self.L.selenite_comb_set_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, self.L.selenite_comb_error_string(self.h).decode())
+
+    def close(self):
+        if self.h:
+            self.L.selenite_comb_free(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
