@@ -2,8 +2,8 @@
 // analysis bank of K = 64 or 512 channels, decimated by D = K / oversample.  Output m of a call:
 //     arm_dot_prod_f32 (BasicMathFunctions/arm_dot_prod_f32.c) per FFT position and rail over the P samples K apart: acc = +0.0f,
 //                      acc = acc + g[r + t K] * s[r + t K], product rounded, then the sum;
-//     arm_cfft_f32(&arm_cfft_sR_f32_lenK, v, 0, 1)  (TransformFunctions/arm_cfft_f32.c:562-616): the transform rx_spectrum.hip restates,
-//                      with its lane layout (rx_fft8.h; the head of rx_spectrum.hip describes the passes and both LDS exchanges).
+//     arm_cfft_f32(&arm_cfft_sR_f32_lenK, v, 0, 1)  (TransformFunctions/arm_cfft_f32.c:562-616): fft8_passes (rx_fft8.h), one transform of
+//                      512 or eight of 64 per wave.
 // Compiled with -ffp-contract=off and IEEE denormals: bit-exact against the composition of the reference's functions.
 //
 // The sum over r lands at v[(r + n0) mod K], n0 = (position + (m + 1) D) mod K: FFT position p always holds the samples whose ABSOLUTE index
@@ -17,8 +17,8 @@
 // wants (K = 512: eight 512-byte wave loads per output).
 //
 // Unit of work: one single-wave workgroup = one band (K = 512) or eight bands (K = 64: lane 8 f + j owns positions j + 8 m of band slot f, the
-// layout of k_spectrum<64>; slots past the last band idle) x a run of kChanRun = 64 consecutive outputs, in tiles of kChanT = 16: the longer
-// the run, the less the overlap at its start weighs (P 16, oversample 1: 15 K samples in front of 64 K).  A tile's K x 16 results are
+// load layout of fft8_passes<64>; slots past the last band idle) x a run of kPfbRun = 64 consecutive outputs, in tiles of kPfbT = 16 (pfb.h): the
+// longer the run, the less the overlap at its start weighs (P 16, oversample 1: 15 K samples in front of 64 K).  A tile's K x 16 results are
 // transposed through LDS (row stride 17 float2: conflict-free writes) and every store instruction covers four channel rows x 128 contiguous
 // bytes; rows of bins nobody selected are never stored.  The taps sit in LDS, loaded once per workgroup.  The loads of a step are
 // unconditional (they are always the call's own samples) and in flight together; those of the run's start choose between the history and
@@ -30,37 +30,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cmath>
 #include <string>
-#include <vector>
 
 #include "../../include/selenite_chan.h"
 #include "../../include/selenite_rx.h"
+#include "pfb.h"
 #include "rx_device.h"
-#include "rx_fft8.h"
 
-struct selenite_chan {
-    uint32_t bands = 0, K = 0, ovs = 0, P = 0, n_bins = 0;
-    bool all_bins = true;
-    int device = 0;
-    float *d_taps = nullptr, *d_tw = nullptr;
-    uint32_t *d_bins = nullptr;
-    float *d_hist[2] = { nullptr, nullptr };     // [bands][K P - D][2]; d_hist[cur] is the state
-    int cur = 0;
-    uint64_t position = 0;
-    hipStream_t stream = nullptr, own_stream = nullptr;
-    int status = 0;
-    std::string err;
-    uint32_t D() const { return K / ovs; }
-    size_t H() const { return (size_t)K * P - D(); }
-};
+struct selenite_chan : srx::PfbObject {};      // history [bands][K P - D][2]
 
 namespace srx {
 namespace {
-
-constexpr int kChanT = 16;          // outputs per tile: 16 x 8 bytes = one 128-byte piece of a channel row
-constexpr int kChanRun = 64;        // outputs per workgroup
-constexpr int kChanRow = 17;        // the LDS tile's row stride in float2: lanes that write one output of 64 rows hit 32 bank pairs once each
 
 struct ChanParams {
     uint32_t bands, n_bins, nout, block_size;
@@ -72,35 +52,27 @@ struct ChanParams {
     float *dst;                     // [bands n_bins][nout][2]
 };
 
-__device__ __forceinline__ float2 chan_load(const float *x, int64_t v) { return reinterpret_cast<const float2 *>(x)[v]; }
-__device__ __forceinline__ float2 chan_load(const int16_t *x, int64_t v)
-{
-    const short2 s = reinterpret_cast<const short2 *>(x)[v];
-    return make_float2(q15_to_float(s.x), q15_to_float(s.y));      // arm_q15_to_float
-}
-
 template <int K, int P, int OVS, typename TIn>
 __global__ __launch_bounds__(64) void k_chan(ChanParams q, const TIn *__restrict__ src)
 {
     constexpr int D = K / OVS, H = K * P - D;
     constexpr int NS = K == 512 ? 1 : 8;                     // band slots of the wave
     constexpr uint32_t HALF = OVS == 2 ? 4u : 0u;            // m ^ 4 = position ^ (K / 2)
-    __shared__ float2 tile[NS * K * kChanRow];
-    __shared__ float2 fs[576];                               // the exchanges of the transform, as in k_spectrum
+    __shared__ float2 tile[NS * K * kPfbRow];
+    __shared__ float2 fs[576];                               // the exchanges of fft8_passes
     __shared__ float gs[K * P];
 
     const uint32_t lane = threadIdx.x, j2 = lane & 7u, g = lane >> 3;
     const uint32_t b = K == 512 ? blockIdx.x : blockIdx.x * 8u + g;
     const bool have = b < q.bands;
-    const uint32_t o0 = blockIdx.y * (uint32_t)kChanRun;
-    const uint32_t nR = q.nout - o0 < (uint32_t)kChanRun ? q.nout - o0 : (uint32_t)kChanRun;
+    const uint32_t o0 = blockIdx.y * (uint32_t)kPfbRun;
+    const uint32_t nR = q.nout - o0 < (uint32_t)kPfbRun ? q.nout - o0 : (uint32_t)kPfbRun;
     const uint32_t e0 = K == 512 ? lane : j2, es = K == 512 ? 64u : 8u;     // the lane owns positions e0 + es * m
 
     for (uint32_t i = lane; i < (uint32_t)(K * P); i += kWave) gs[i] = q.taps[i];
     float2 tw1[7], tw2[7];
 #pragma unroll
-    for (int k = 1; k < 8; ++k) {
-        // pass n2 = 64 (twidCoefModifier 1): ia_k = k * j; pass n2 = 8 (modifier K / 64): ia_k = k * j * K / 64 (arm_cfft_radix8_f32.c:146-168)
+    for (int k = 1; k < 8; ++k) {      // fft8_twiddles<K> (rx_fft8.h), kept inline: the call costs K = 512 an instruction (profiles/pfb_shared/README.md)
         if (K == 512) tw1[k - 1] = reinterpret_cast<const float2 *>(q.tw)[k * lane];
         tw2[k - 1] = reinterpret_cast<const float2 *>(q.tw)[(K / 64) * k * j2];
     }
@@ -115,10 +87,10 @@ __global__ __launch_bounds__(64) void k_chan(ChanParams q, const TIn *__restrict
     auto elem = [&](int64_t v) -> float2 {                   // anywhere at or behind the run's start
         if (!have || v < -(int64_t)H || v > last) return zero;
         if (v < 0) return reinterpret_cast<const float2 *>(hb)[v + H];
-        return chan_load(x, v);
+        return load_iq(x, v);
     };
     auto fresh = [&](int64_t v) -> float2 {                  // a sample the window moves over inside the run: always one of the call's own
-        const float2 fx = chan_load(x, v);
+        const float2 fx = load_iq(x, v);
         return have ? fx : zero;
     };
 
@@ -161,48 +133,19 @@ __global__ __launch_bounds__(64) void k_chan(ChanParams q, const TIn *__restrict
         }
         float2 a[8];
 #pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const uint32_t r = e0 + es * ((uint32_t)m ^ (PAR ? HALF : 0u));
-            float ai = 0.0f, aq = 0.0f;
-#pragma unroll
-            for (int t = 0; t < P; ++t) {
-                const float c = gs[r + (uint32_t)(t * K)];
-                const float pi = c * h[m][t].x, pq = c * h[m][t].y;
-                ai = ai + pi;
-                aq = aq + pq;
-            }
-            a[m] = make_float2(ai, aq);
-        }
-        if (K == 512) {
-            bfly8(a);
-            if (lane != 0u) twiddle7(a, tw1);
-            __syncthreads();
-#pragma unroll
-            for (int m = 0; m < 8; ++m) fs[lane + 72u * m] = a[m];
-            __syncthreads();
-#pragma unroll
-            for (int m = 0; m < 8; ++m) a[m] = fs[72u * g + j2 + 8u * m];
-        }
-        bfly8(a);
-        if (j2 != 0u) twiddle7(a, tw2);
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < 8; ++m) fs[72u * g + j2 + 9u * m] = a[m];
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < 8; ++m) a[m] = fs[9u * lane + m];
-        bfly8(a);                                            // n2 = 1: every butterfly is of the twiddle-free form
+        for (int m = 0; m < 8; ++m) a[m] = pfb_dot<K>(gs, e0 + es * ((uint32_t)m ^ (PAR ? HALF : 0u)), h[m]);
+        fft8_passes<K>(a, tw1, tw2, fs, lane);
         // K = 512: position 8 * lane + m = digits (g, j2, m) holds bin 64 m + 8 j2 + g; K = 64: position 8 * j2 + m of slot g holds bin 8 m + j2
         // (arm_bitreversal_32: base-8 digit reversal)
         const uint32_t row0 = K == 512 ? 8u * j2 + g : 64u * g + j2, rs = K == 512 ? 64u : 8u;
 #pragma unroll
-        for (int m = 0; m < 8; ++m) tile[(row0 + rs * m) * kChanRow + oi] = a[m];
+        for (int m = 0; m < 8; ++m) tile[(row0 + rs * m) * kPfbRow + oi] = a[m];
     };
 
     const uint32_t c = lane & 15u;
 #pragma unroll 1
-    for (uint32_t t0 = 0; t0 < nR; t0 += (uint32_t)kChanT) {
-        const uint32_t nT = nR - t0 < (uint32_t)kChanT ? nR - t0 : (uint32_t)kChanT;
+    for (uint32_t t0 = 0; t0 < nR; t0 += (uint32_t)kPfbT) {
+        const uint32_t nT = nR - t0 < (uint32_t)kPfbT ? nR - t0 : (uint32_t)kPfbT;
 #pragma unroll 1
         for (uint32_t oi = 0; oi < nT; ++oi) {
             const int64_t E = E0 + (int64_t)(t0 + oi + 1u) * D;
@@ -219,7 +162,7 @@ __global__ __launch_bounds__(64) void k_chan(ChanParams q, const TIn *__restrict
                 if (c >= nT) continue;
                 const uint32_t bin = q.bins ? q.bins[i] : i;
                 const int64_t at = ((int64_t)bs * q.n_bins + i) * q.nout + o0 + t0 + c;
-                reinterpret_cast<float2 *>(q.dst)[at] = tile[(s * (uint32_t)K + bin) * kChanRow + c];
+                reinterpret_cast<float2 *>(q.dst)[at] = tile[(s * (uint32_t)K + bin) * kPfbRow + c];
             }
         }
         __syncthreads();
@@ -235,7 +178,7 @@ __global__ __launch_bounds__(256) void k_chan_hist(const TIn *__restrict__ src, 
     if (i >= H) return;
     const int64_t j = (int64_t)i + block_size;
     const float2 v = j < (int64_t)H ? reinterpret_cast<const float2 *>(old)[(int64_t)b * H + j]
-                                    : chan_load(src + (int64_t)b * block_size * 2, j - H);
+                                    : load_iq(src + (int64_t)b * block_size * 2, j - H);
     reinterpret_cast<float2 *>(neu)[(int64_t)b * H + i] = v;
 }
 
@@ -256,25 +199,12 @@ void launch_k(uint32_t P, uint32_t ovs, dim3 grid, hipStream_t st, const ChanPar
     }
 }
 
-int fail(selenite_chan *Ch, int code, const std::string &msg)
-{
-    if (Ch && Ch->status == 0) { Ch->status = code; Ch->err = msg; }
-    return code;
-}
-
-#define CCHK(Ch, call)                                                                         \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail((Ch), SELENITE_RX_DEVICE_ERROR, std::string(#call ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
 // 0 where the call would be refused
 uint32_t out_len(const selenite_chan *Ch, uint32_t block_size)
 {
     if (!Ch || block_size == 0 || block_size % Ch->D() != 0) return 0;
     const uint32_t nout = block_size / Ch->D();
-    return (nout + kChanRun - 1) / kChanRun > 65535u ? 0 : nout;          // (the runs are the grid's y)
+    return (nout + kPfbRun - 1) / kPfbRun > 65535u ? 0 : nout;          // (the runs are the grid's y)
 }
 
 template <typename TIn>
@@ -285,34 +215,25 @@ int process(selenite_chan *Ch, const TIn *src, float *dst, uint32_t block_size, 
     const uint32_t nout = out_len(Ch, block_size);
     if (!nout)
         return fail(Ch, SELENITE_RX_LENGTH_ERROR, std::string(who) + ": blockSize is not a non-zero multiple of fft_len / oversample (or longer than 64 x 65535 outputs)");
-    CCHK(Ch, hipSetDevice(Ch->device));
+    PFB_CHK(Ch, hipSetDevice(Ch->device));
     ChanParams q{};
     q.bands = Ch->bands; q.n_bins = Ch->n_bins; q.nout = nout; q.block_size = block_size;
     q.poff = (uint32_t)(Ch->position % Ch->K);
     q.taps = Ch->d_taps; q.tw = Ch->d_tw; q.hist = Ch->d_hist[Ch->cur]; q.bins = Ch->all_bins ? nullptr : Ch->d_bins; q.dst = dst;
-    const uint32_t runs = (nout + kChanRun - 1) / kChanRun;
+    const uint32_t runs = (nout + kPfbRun - 1) / kPfbRun;
     if (Ch->K == 512) launch_k<512, TIn>(Ch->P, Ch->ovs, dim3(Ch->bands, runs), Ch->stream, q, src);
     else launch_k<64, TIn>(Ch->P, Ch->ovs, dim3((Ch->bands + 7u) / 8u, runs), Ch->stream, q, src);
-    CCHK(Ch, hipGetLastError());
-    const uint32_t H = (uint32_t)Ch->H();
+    PFB_CHK(Ch, hipGetLastError());
+    const uint32_t H = Ch->K * Ch->P - Ch->D();
     // gridDim.y is limited to 65535: loop over band slabs (as launch_synth does over channels)
     for (uint32_t b0 = 0; b0 < Ch->bands; b0 += 32768u) {
         const uint32_t n = Ch->bands - b0 < 32768u ? Ch->bands - b0 : 32768u;
         hipLaunchKernelGGL((k_chan_hist<TIn>), dim3((H + 255u) / 256u, n), dim3(256), 0, Ch->stream, src, Ch->d_hist[Ch->cur],
                            Ch->d_hist[1 - Ch->cur], H, block_size, b0);
     }
-    CCHK(Ch, hipGetLastError());
+    PFB_CHK(Ch, hipGetLastError());
     Ch->cur = 1 - Ch->cur;
     Ch->position += block_size;
-    return SELENITE_RX_SUCCESS;
-}
-
-int reset(selenite_chan *Ch)
-{
-    CCHK(Ch, hipSetDevice(Ch->device));
-    CCHK(Ch, hipMemsetAsync(Ch->d_hist[Ch->cur], 0, (size_t)Ch->bands * Ch->H() * 2 * sizeof(float), Ch->stream));
-    CCHK(Ch, hipStreamSynchronize(Ch->stream));
-    Ch->position = 0;
     return SELENITE_RX_SUCCESS;
 }
 
@@ -327,99 +248,30 @@ extern "C" int selenite_chan_init(selenite_chan **out, const selenite_chan_confi
     *out = nullptr;
     // everything is validated before the device is touched
     if (!cfg || cfg->struct_size != sizeof(selenite_chan_config)) return SELENITE_RX_ARGUMENT_ERROR;
-    if (cfg->fft_len != 64 && cfg->fft_len != 512) return SELENITE_RX_LENGTH_ERROR;     // the pure radix-8 lengths of arm_cfft_f32
-    const uint32_t K = cfg->fft_len, P = cfg->taps_per_branch;
-    if (cfg->bands == 0 || (cfg->oversample != 1 && cfg->oversample != 2) || (P != 4 && P != 8 && P != 12 && P != 16) ||
-        cfg->n_bins == 0 || cfg->reserved != 0 || !cfg->coeffs)
-        return SELENITE_RX_ARGUMENT_ERROR;
-    if (cfg->bands > SELENITE_CHAN_MAX_BANDS) return SELENITE_RX_ARGUMENT_ERROR;        // (the bands are k_chan's grid x: 64 threads each, under 2^32)
-    if ((uint64_t)cfg->bands * cfg->n_bins > 0xFFFFFFFFull) return SELENITE_RX_ARGUMENT_ERROR;
-    if (!cfg->bins && cfg->n_bins != K) return SELENITE_RX_ARGUMENT_ERROR;
-    for (uint32_t i = 0; i < K * P; ++i)
-        if (!std::isfinite(cfg->coeffs[i])) return SELENITE_RX_ARGUMENT_ERROR;
-    if (cfg->bins)
-        for (uint32_t i = 0; i < cfg->n_bins; ++i)
-            if (cfg->bins[i] >= K) return SELENITE_RX_ARGUMENT_ERROR;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SELENITE_RX_DEVICE_ERROR;      // no CPU fallback
+    if (int rc = pfb_validate(cfg, SELENITE_CHAN_MAX_BANDS, true)) return rc;
+    const size_t H = (size_t)cfg->fft_len * cfg->taps_per_branch - cfg->fft_len / cfg->oversample;
     selenite_chan *Ch = new selenite_chan;
-    Ch->bands = cfg->bands; Ch->K = K; Ch->ovs = cfg->oversample; Ch->P = P; Ch->n_bins = cfg->n_bins; Ch->all_bins = !cfg->bins;
-    auto bail = [&](int code) { selenite_chan_free(Ch); return code; };
-    if (hipGetDevice(&Ch->device) != hipSuccess) return bail(SELENITE_RX_DEVICE_ERROR);
-    if (hipStreamCreateWithFlags(&Ch->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(SELENITE_RX_DEVICE_ERROR);
-    Ch->stream = Ch->own_stream;
-    std::vector<float> tw(2 * (size_t)K);
-    spec_twiddles(tw.data(), K);
-    const size_t hist_bytes = (size_t)Ch->bands * Ch->H() * 2 * sizeof(float);
-    if (hipMalloc((void **)&Ch->d_taps, (size_t)K * P * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&Ch->d_tw, tw.size() * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&Ch->d_hist[0], hist_bytes) != hipSuccess || hipMalloc((void **)&Ch->d_hist[1], hist_bytes) != hipSuccess ||
-        (cfg->bins && hipMalloc((void **)&Ch->d_bins, (size_t)cfg->n_bins * sizeof(uint32_t)) != hipSuccess))
-        return bail(SELENITE_RX_DEVICE_ERROR);
-    if (hipMemcpy(Ch->d_taps, cfg->coeffs, (size_t)K * P * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(Ch->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        (cfg->bins && hipMemcpy(Ch->d_bins, cfg->bins, (size_t)cfg->n_bins * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess))
-        return bail(SELENITE_RX_DEVICE_ERROR);
-    if (reset(Ch)) return bail(SELENITE_RX_DEVICE_ERROR);
+    if (int rc = pfb_create(Ch, cfg, (size_t)cfg->bands * H * 2 * sizeof(float))) {
+        pfb_free(Ch);
+        return rc;
+    }
     *out = Ch;
     return SELENITE_RX_SUCCESS;
 }
 
-extern "C" void selenite_chan_free(selenite_chan *Ch)
-{
-    if (!Ch) return;
-    if (Ch->stream) (void)hipStreamSynchronize(Ch->stream);
-    void *ptrs[] = { Ch->d_taps, Ch->d_tw, Ch->d_bins, Ch->d_hist[0], Ch->d_hist[1] };
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (Ch->own_stream) (void)hipStreamDestroy(Ch->own_stream);
-    delete Ch;
-}
-
+extern "C" void selenite_chan_free(selenite_chan *Ch) { pfb_free(Ch); }
 extern "C" int selenite_chan_status(const selenite_chan *Ch) { return Ch ? Ch->status : SELENITE_RX_ARGUMENT_ERROR; }
 extern "C" const char *selenite_chan_error_string(const selenite_chan *Ch) { return Ch ? Ch->err.c_str() : "null channeliser"; }
-
-extern "C" int selenite_chan_set_stream(selenite_chan *Ch, void *hip_stream)
-{
-    if (!Ch) return SELENITE_RX_ARGUMENT_ERROR;
-    CCHK(Ch, hipStreamSynchronize(Ch->stream));
-    Ch->stream = hip_stream ? (hipStream_t)hip_stream : Ch->own_stream;
-    return SELENITE_RX_SUCCESS;
-}
-
-extern "C" int selenite_chan_sync(selenite_chan *Ch)
-{
-    if (!Ch) return SELENITE_RX_ARGUMENT_ERROR;
-    CCHK(Ch, hipStreamSynchronize(Ch->stream));
-    return Ch->status;
-}
-
-extern "C" int selenite_chan_reset(selenite_chan *Ch)
-{
-    if (!Ch) return SELENITE_RX_ARGUMENT_ERROR;
-    return reset(Ch);
-}
-
+extern "C" int selenite_chan_set_stream(selenite_chan *Ch, void *hip_stream) { return pfb_set_stream(Ch, hip_stream); }
+extern "C" int selenite_chan_sync(selenite_chan *Ch) { return pfb_sync(Ch); }
+extern "C" int selenite_chan_reset(selenite_chan *Ch) { return Ch ? pfb_reset(Ch) : SELENITE_RX_ARGUMENT_ERROR; }
 extern "C" int selenite_chan_get_state(selenite_chan *Ch, const selenite_chan_state_view *v)
 {
-    if (!Ch || !v) return SELENITE_RX_ARGUMENT_ERROR;
-    CCHK(Ch, hipSetDevice(Ch->device));
-    CCHK(Ch, hipStreamSynchronize(Ch->stream));
-    if (v->history) CCHK(Ch, hipMemcpy(v->history, Ch->d_hist[Ch->cur], (size_t)Ch->bands * Ch->H() * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    if (v->position) *v->position = Ch->position;
-    return SELENITE_RX_SUCCESS;
+    return pfb_state_copy(Ch, v, true, "selenite_chan_get_state");
 }
-
 extern "C" int selenite_chan_set_state(selenite_chan *Ch, const selenite_chan_state_view *v)
 {
-    if (!Ch || !v) return SELENITE_RX_ARGUMENT_ERROR;
-    if (v->position && *v->position % Ch->D() != 0)
-        return fail(Ch, SELENITE_RX_ARGUMENT_ERROR, "selenite_chan_set_state: position is not a multiple of fft_len / oversample");
-    CCHK(Ch, hipSetDevice(Ch->device));
-    CCHK(Ch, hipStreamSynchronize(Ch->stream));
-    if (v->history) CCHK(Ch, hipMemcpy(Ch->d_hist[Ch->cur], v->history, (size_t)Ch->bands * Ch->H() * 2 * sizeof(float), hipMemcpyHostToDevice));
-    if (v->position) Ch->position = *v->position;
-    return SELENITE_RX_SUCCESS;
+    return pfb_state_copy(Ch, v, false, "selenite_chan_set_state");
 }
 
 extern "C" uint32_t selenite_chan_out_channels(const selenite_chan *Ch) { return Ch ? Ch->bands * Ch->n_bins : 0; }

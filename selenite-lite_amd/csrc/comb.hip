@@ -1,13 +1,13 @@
 // comb.hip -- polyphase combiner (include/selenite_comb.h): per wideband stream ("band") a weighted-overlap-add
 // synthesis bank of K = 64 or 512 channels, interpolated by D = K / oversample: the channeliser (chan.hip) run backwards.  Per input frame f:
-//     arm_cfft_f32(&arm_cfft_sR_f32_lenK, v, 1, 1)  (TransformFunctions/arm_cfft_f32.c:562-616): imag negated, the passes chan.hip and
-//                      rx_spectrum.hip run (rx_fft8.h, their lane layout and LDS exchanges), re * invL and (-im) * invL -> u_f[0 .. K - 1];
+//     arm_cfft_f32(&arm_cfft_sR_f32_lenK, v, 1, 1)  (TransformFunctions/arm_cfft_f32.c:562-616): imag negated, the passes of fft8_passes
+//                      (rx_fft8.h, which explains the layout; this kernel holds them inline), re * invL and (-im) * invL -> u_f[0 .. K - 1];
 //     arm_dot_prod_f32 (BasicMathFunctions/arm_dot_prod_f32.c) per output sample and rail over the Q = P * oversample frames that overlap in
 //                      it: out[f D + j] = sum_t g[(D - 1 - j) + t D] * u_{f - Q + 1 + t}[p], p = (f D + j) mod K, acc = +0.0f, product rounded,
 //                      then the sum, t ascending.
 // Compiled with -ffp-contract=off and IEEE denormals: bit-exact against the composition of the reference's functions.
 //
-// Behind the passes a lane holds eight time-domain positions p = pb + es * m (the digit-reversed layout k_chan stores its bins from: es = 64 or
+// Behind the passes a lane holds eight time-domain positions p = pb + es * m (the digit-reversed layout fft8_passes returns: es = 64 or
 // 8).  It keeps, per owned position, the Q newest u[p] as a shift register in VGPRs (8 Q float2: 256 VGPRs at Q = 16, which is why Q <= 16);
 // every register shifts on every frame.
 //   oversample 1  a frame emits all K positions, j = p;
@@ -15,10 +15,10 @@
 //                 position / D + frame -- with j = p mod D = pb + es * (m & 3): two straight-line forms chosen by a uniform branch.
 //
 // Unit of work: one single-wave workgroup = one band (K = 512) or eight bands (K = 64: lane 8 s + j2 works for band slot s; slots past the last
-// band idle) x a run of kCombRun = 64 consecutive frames (the grid's y), in tiles of kCombT = 16.  The rows of one frame lie nin * 8 bytes
+// band idle) x a run of kPfbRun = 64 consecutive frames (the grid's y), in tiles of kPfbT = 16 (pfb.h).  The rows of one frame lie nin * 8 bytes
 // apart, so a tile is loaded row-wise -- 16 frames = 128 contiguous bytes per row, four rows per wave instruction, kCombLoads = 8 such loads
 // in flight before the first is written (a single wave has nothing else to hide their latency behind) -- into an LDS
-// tile [K][17] float2 (k_chan's store tile run backwards); the rows of bins nobody feeds are zeroed once and never written.  The Q - 1 frames in
+// tile [K][17] float2; the rows of bins nobody feeds are zeroed once and never written.  The Q - 1 frames in
 // front of a run are loaded and transformed the same way, from the history (the call's first run) or from the call (every other run: a run
 // is longer than Q - 1), and emit nothing: (Q - 1) / 64 extra transforms.  A frame's D results go through LDS and leave as contiguous
 // stores (K = 512: 512 bytes per wave instruction; K = 64: 256 bytes per band slot, 128 as int16); the int16 instantiation converts in
@@ -29,40 +29,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cmath>
 #include <string>
 #include <vector>
 
 #include "../../include/selenite_chan.h"
 #include "../../include/selenite_comb.h"
 #include "../../include/selenite_rx.h"
+#include "pfb.h"
 #include "rx_device.h"
-#include "rx_fft8.h"
 
-struct selenite_comb {
-    uint32_t bands = 0, K = 0, ovs = 0, P = 0, n_bins = 0, round = 0;
-    bool all_bins = true;
-    int device = 0;
-    float *d_taps = nullptr, *d_tw = nullptr;
-    uint32_t *d_bins = nullptr;
-    float *d_hist[2] = { nullptr, nullptr };     // [bands n_bins][Q - 1][2]; d_hist[cur] is the state
-    int cur = 0;
-    uint64_t position = 0;
-    hipStream_t stream = nullptr, own_stream = nullptr;
-    int status = 0;
-    std::string err;
-    uint32_t D() const { return K / ovs; }
+struct selenite_comb : srx::PfbObject {          // history [bands n_bins][Q - 1][2]
+    uint32_t round = 0;
     uint32_t Q() const { return P * ovs; }
     size_t rows() const { return (size_t)bands * n_bins; }
-    size_t hist_bytes() const { return rows() * (Q() - 1) * 2 * sizeof(float); }
 };
 
 namespace srx {
 namespace {
 
-constexpr int kCombT = 16;          // frames per tile: 16 x 8 bytes = one 128-byte piece of a channel row
-constexpr int kCombRun = 64;        // frames per workgroup
-constexpr int kCombRow = 17;        // the LDS tile's row stride in float2 (k_chan's kChanRow)
 constexpr int kCombLoads = 8;       // wave loads of the input tile in flight together
 
 struct CombParams {
@@ -97,15 +81,15 @@ __global__ __launch_bounds__(64) void k_comb(CombParams q, TOut *__restrict__ ds
     constexpr int SD = D + 8;                                // a slot's stride in the output exchange
     constexpr float invL = 1.0f / (float)K;                  // arm_cfft_f32.c:606
     typedef typename CombOut<TOut>::pair Pair;
-    __shared__ float2 tile[NS * K * kCombRow];
-    __shared__ float2 fs[576];                               // the exchanges of the transform, as in k_spectrum and k_chan
+    __shared__ float2 tile[NS * K * kPfbRow];
+    __shared__ float2 fs[576];                               // the exchanges of fft8_passes
     __shared__ float gs[D * Q];                              // K P taps
     __shared__ Pair os[NS * SD];                             // a frame's results, in output order
     __shared__ uint32_t binl[K];                             // the bin of input row i
 
     const uint32_t lane = threadIdx.x, j2 = lane & 7u, g = lane >> 3;
-    const uint32_t o0 = blockIdx.y * (uint32_t)kCombRun;
-    const uint32_t nR = q.nin - o0 < (uint32_t)kCombRun ? q.nin - o0 : (uint32_t)kCombRun;
+    const uint32_t o0 = blockIdx.y * (uint32_t)kPfbRun;
+    const uint32_t nR = q.nin - o0 < (uint32_t)kPfbRun ? q.nin - o0 : (uint32_t)kPfbRun;
     const uint32_t es = K == 512 ? 64u : 8u;
     const uint32_t e0 = K == 512 ? lane : 64u * g + j2;      // pass 1 reads the tile rows e0 + es * m (K = 64: bins j2 + 8 m of slot g)
     // behind the passes a[m] is time-domain position pb + es * m (arm_bitreversal_32: base-8 digit reversal; K = 512: position 8 * lane + m =
@@ -116,11 +100,12 @@ __global__ __launch_bounds__(64) void k_comb(CombParams q, TOut *__restrict__ ds
     const float2 zero = make_float2(0.0f, 0.0f);
     for (uint32_t i = lane; i < (uint32_t)(D * Q); i += kWave) gs[i] = q.taps[i];
     for (uint32_t i = lane; i < q.n_bins; i += kWave) binl[i] = q.bins ? q.bins[i] : i;
-    for (uint32_t i = lane; i < (uint32_t)(NS * K * kCombRow); i += kWave) tile[i] = zero;      // rows of unfed bins and idle slots stay +0.0f
+    for (uint32_t i = lane; i < (uint32_t)(NS * K * kPfbRow); i += kWave) tile[i] = zero;      // rows of unfed bins and idle slots stay +0.0f
     float2 tw1[7], tw2[7];
+    // The twiddle gather, the passes and the tap sum below are fft8_twiddles / fft8_passes (rx_fft8.h) and pfb_dot (pfb.h) kept inline: with the
+    // calls this kernel's register allocation and schedule move and some instantiations get slower (profiles/pfb_shared/README.md)
 #pragma unroll
     for (int k = 1; k < 8; ++k) {
-        // pass n2 = 64 (twidCoefModifier 1): ia_k = k * j; pass n2 = 8 (modifier K / 64): ia_k = k * j * K / 64 (arm_cfft_radix8_f32.c:146-168)
         if (K == 512) tw1[k - 1] = reinterpret_cast<const float2 *>(q.tw)[k * lane];
         tw2[k - 1] = reinterpret_cast<const float2 *>(q.tw)[(K / 64) * k * j2];
     }
@@ -139,10 +124,10 @@ __global__ __launch_bounds__(64) void k_comb(CombParams q, TOut *__restrict__ ds
         float2 a[8];
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-            const float2 v = tile[(e0 + es * (uint32_t)m) * kCombRow + ci];
+            const float2 v = tile[(e0 + es * (uint32_t)m) * kPfbRow + ci];
             a[m] = make_float2(v.x, -v.y);                   // arm_cfft_f32.c:571-580
         }
-        if (K == 512) {
+        if (K == 512) {                                      // fft8_passes<K>, inline (see above)
             bfly8(a);
             if (lane != 0u) twiddle7(a, tw1);
             __syncthreads();
@@ -160,7 +145,7 @@ __global__ __launch_bounds__(64) void k_comb(CombParams q, TOut *__restrict__ ds
         __syncthreads();
 #pragma unroll
         for (int m = 0; m < 8; ++m) a[m] = fs[9u * lane + m];
-        bfly8(a);                                            // n2 = 1: every butterfly is of the twiddle-free form
+        bfly8(a);
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
 #pragma unroll
@@ -178,7 +163,7 @@ __global__ __launch_bounds__(64) void k_comb(CombParams q, TOut *__restrict__ ds
             if (OVS == 2 && ((m >= 4) != (PAR == 1u))) continue;
             const uint32_t jj = pb + es * (uint32_t)(OVS == 2 ? (m & 3) : m);      // j = p mod D
             const uint32_t r = (uint32_t)(D - 1) - jj;
-            float ai = 0.0f, aq = 0.0f;
+            float ai = 0.0f, aq = 0.0f;                      // pfb_dot<D>, inline (see above)
 #pragma unroll
             for (int t = 0; t < Q; ++t) {
                 const float c = gs[r + (uint32_t)(t * D)];
@@ -200,9 +185,9 @@ __global__ __launch_bounds__(64) void k_comb(CombParams q, TOut *__restrict__ ds
     const uint32_t c = lane & 15u;
     // tile -1 is the run's start: the Q - 1 frames in front of it, which emit nothing
 #pragma unroll 1
-    for (int32_t t0 = -kCombT; t0 < (int32_t)nR; t0 += kCombT) {
+    for (int32_t t0 = -kPfbT; t0 < (int32_t)nR; t0 += kPfbT) {
         const bool pro = t0 < 0;
-        const uint32_t nT = pro ? (uint32_t)(Q - 1) : (nR - (uint32_t)t0 < (uint32_t)kCombT ? nR - (uint32_t)t0 : (uint32_t)kCombT);
+        const uint32_t nT = pro ? (uint32_t)(Q - 1) : (nR - (uint32_t)t0 < (uint32_t)kPfbT ? nR - (uint32_t)t0 : (uint32_t)kPfbT);
         const bool from_hist = pro && o0 == 0u;
         const float2 *base = reinterpret_cast<const float2 *>(from_hist ? q.hist : q.src);
         const int64_t stride = from_hist ? (int64_t)(Q - 1) : (int64_t)q.nin;
@@ -222,7 +207,7 @@ __global__ __launch_bounds__(64) void k_comb(CombParams q, TOut *__restrict__ ds
 #pragma unroll
                 for (int u = 0; u < kCombLoads; ++u) {
                     const uint32_t i = i0 + 4u * (uint32_t)u;
-                    if (i < q.n_bins && c < nT) tile[(s * (uint32_t)K + binl[i]) * kCombRow + c] = v[u];
+                    if (i < q.n_bins && c < nT) tile[(s * (uint32_t)K + binl[i]) * kPfbRow + c] = v[u];
                 }
             }
         }
@@ -271,24 +256,11 @@ void launch_k(uint32_t Q, uint32_t ovs, dim3 grid, hipStream_t st, const CombPar
     }
 }
 
-int fail(selenite_comb *Cb, int code, const std::string &msg)
-{
-    if (Cb && Cb->status == 0) { Cb->status = code; Cb->err = msg; }
-    return code;
-}
-
-#define BCHK(Cb, call)                                                                         \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail((Cb), SELENITE_RX_DEVICE_ERROR, std::string(#call ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
 // 0 where the call would be refused
 uint32_t out_len(const selenite_comb *Cb, uint32_t block_size)
 {
     if (!Cb || block_size == 0) return 0;
-    if (block_size > (uint32_t)kCombRun * 65535u) return 0;                               // (the runs are the grid's y)
+    if (block_size > (uint32_t)kPfbRun * 65535u) return 0;                               // (the runs are the grid's y)
     const uint64_t n = (uint64_t)block_size * Cb->D();
     return n > 0xFFFFFFFFull ? 0 : (uint32_t)n;
 }
@@ -300,33 +272,24 @@ int process(selenite_comb *Cb, const float *src, TOut *dst, uint32_t block_size,
     if (!src || !dst) return fail(Cb, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": NULL buffer");
     if (!out_len(Cb, block_size))
         return fail(Cb, SELENITE_RX_LENGTH_ERROR, std::string(who) + ": blockSize is zero or longer than 64 x 65535 frames");
-    BCHK(Cb, hipSetDevice(Cb->device));
+    PFB_CHK(Cb, hipSetDevice(Cb->device));
     CombParams q{};
     q.bands = Cb->bands; q.n_bins = Cb->n_bins; q.nin = block_size;
     q.par0 = (uint32_t)((Cb->position / Cb->D()) & 1u); q.round = Cb->round;
     q.taps = Cb->d_taps; q.tw = Cb->d_tw; q.hist = Cb->d_hist[Cb->cur]; q.bins = Cb->all_bins ? nullptr : Cb->d_bins; q.src = src;
-    const uint32_t runs = (block_size + kCombRun - 1) / kCombRun;
+    const uint32_t runs = (block_size + kPfbRun - 1) / kPfbRun;
     if (Cb->K == 512) launch_k<512, TOut>(Cb->Q(), Cb->ovs, dim3(Cb->bands, runs), Cb->stream, q, dst);
     else launch_k<64, TOut>(Cb->Q(), Cb->ovs, dim3((Cb->bands + 7u) / 8u, runs), Cb->stream, q, dst);
-    BCHK(Cb, hipGetLastError());
+    PFB_CHK(Cb, hipGetLastError());
     // (bands n_bins < 2^32 rows of Q - 1 <= 15 samples: the count needs 64 bits, and one thread each would not be a legal grid)
     const uint32_t Q1 = Cb->Q() - 1;
     const uint64_t total = (uint64_t)Cb->rows() * Q1;
     const uint64_t blocks = (total + 255u) / 256u;
     hipLaunchKernelGGL(k_comb_hist, dim3(blocks < kCombHistBlocks ? (uint32_t)blocks : kCombHistBlocks), dim3(256), 0, Cb->stream, src,
                        Cb->d_hist[Cb->cur], Cb->d_hist[1 - Cb->cur], Q1, block_size, total);
-    BCHK(Cb, hipGetLastError());
+    PFB_CHK(Cb, hipGetLastError());
     Cb->cur = 1 - Cb->cur;
     Cb->position += (uint64_t)block_size * Cb->D();
-    return SELENITE_RX_SUCCESS;
-}
-
-int reset(selenite_comb *Cb)
-{
-    BCHK(Cb, hipSetDevice(Cb->device));
-    BCHK(Cb, hipMemsetAsync(Cb->d_hist[Cb->cur], 0, Cb->hist_bytes(), Cb->stream));
-    BCHK(Cb, hipStreamSynchronize(Cb->stream));
-    Cb->position = 0;
     return SELENITE_RX_SUCCESS;
 }
 
@@ -346,103 +309,39 @@ extern "C" int selenite_comb_init(selenite_comb **out, const selenite_comb_confi
     *out = nullptr;
     // everything is validated before the device is touched
     if (!cfg || cfg->struct_size != sizeof(selenite_comb_config)) return SELENITE_RX_ARGUMENT_ERROR;
-    if (cfg->fft_len != 64 && cfg->fft_len != 512) return SELENITE_RX_LENGTH_ERROR;     // the pure radix-8 lengths of arm_cfft_f32
-    const uint32_t K = cfg->fft_len, P = cfg->taps_per_branch;
-    if (cfg->bands == 0 || !shape_ok(P, cfg->oversample) || cfg->n_bins == 0 || cfg->n_bins > K || cfg->q15_rounding > 1u ||
-        cfg->reserved != 0 || !cfg->coeffs)
-        return SELENITE_RX_ARGUMENT_ERROR;
-    if (cfg->bands > SELENITE_COMB_MAX_BANDS) return SELENITE_RX_ARGUMENT_ERROR;        // (the bands are k_comb's grid x: 64 threads each, under 2^32)
-    if ((uint64_t)cfg->bands * cfg->n_bins > 0xFFFFFFFFull) return SELENITE_RX_ARGUMENT_ERROR;
-    if (!cfg->bins && cfg->n_bins != K) return SELENITE_RX_ARGUMENT_ERROR;
-    for (uint32_t i = 0; i < K * P; ++i)
-        if (!std::isfinite(cfg->coeffs[i])) return SELENITE_RX_ARGUMENT_ERROR;
+    const bool own_ok = shape_ok(cfg->taps_per_branch, cfg->oversample) && cfg->n_bins <= cfg->fft_len && cfg->q15_rounding <= 1u;
+    if (int rc = pfb_validate(cfg, SELENITE_COMB_MAX_BANDS, own_ok)) return rc;
     if (cfg->bins) {
-        std::vector<bool> fed(K, false);
+        std::vector<bool> fed(cfg->fft_len, false);
         for (uint32_t i = 0; i < cfg->n_bins; ++i) {
-            if (cfg->bins[i] >= K || fed[cfg->bins[i]]) return SELENITE_RX_ARGUMENT_ERROR;      // two rows on one bin have no defined sum
+            if (fed[cfg->bins[i]]) return SELENITE_RX_ARGUMENT_ERROR;      // two rows on one bin have no defined sum
             fed[cfg->bins[i]] = true;
         }
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SELENITE_RX_DEVICE_ERROR;      // no CPU fallback
+    const size_t Q1 = cfg->taps_per_branch * cfg->oversample - 1;
     selenite_comb *Cb = new selenite_comb;
-    Cb->bands = cfg->bands; Cb->K = K; Cb->ovs = cfg->oversample; Cb->P = P; Cb->n_bins = cfg->n_bins; Cb->round = cfg->q15_rounding;
-    Cb->all_bins = !cfg->bins;
-    auto bail = [&](int code) { selenite_comb_free(Cb); return code; };
-    if (hipGetDevice(&Cb->device) != hipSuccess) return bail(SELENITE_RX_DEVICE_ERROR);
-    if (hipStreamCreateWithFlags(&Cb->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(SELENITE_RX_DEVICE_ERROR);
-    Cb->stream = Cb->own_stream;
-    std::vector<float> tw(2 * (size_t)K);
-    spec_twiddles(tw.data(), K);
-    if (hipMalloc((void **)&Cb->d_taps, (size_t)K * P * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&Cb->d_tw, tw.size() * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&Cb->d_hist[0], Cb->hist_bytes()) != hipSuccess || hipMalloc((void **)&Cb->d_hist[1], Cb->hist_bytes()) != hipSuccess ||
-        (cfg->bins && hipMalloc((void **)&Cb->d_bins, (size_t)cfg->n_bins * sizeof(uint32_t)) != hipSuccess))
-        return bail(SELENITE_RX_DEVICE_ERROR);
-    if (hipMemcpy(Cb->d_taps, cfg->coeffs, (size_t)K * P * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(Cb->d_tw, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        (cfg->bins && hipMemcpy(Cb->d_bins, cfg->bins, (size_t)cfg->n_bins * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess))
-        return bail(SELENITE_RX_DEVICE_ERROR);
-    if (reset(Cb)) return bail(SELENITE_RX_DEVICE_ERROR);
+    Cb->round = cfg->q15_rounding;
+    if (int rc = pfb_create(Cb, cfg, (size_t)cfg->bands * cfg->n_bins * Q1 * 2 * sizeof(float))) {
+        pfb_free(Cb);
+        return rc;
+    }
     *out = Cb;
     return SELENITE_RX_SUCCESS;
 }
 
-extern "C" void selenite_comb_free(selenite_comb *Cb)
-{
-    if (!Cb) return;
-    if (Cb->stream) (void)hipStreamSynchronize(Cb->stream);
-    void *ptrs[] = { Cb->d_taps, Cb->d_tw, Cb->d_bins, Cb->d_hist[0], Cb->d_hist[1] };
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (Cb->own_stream) (void)hipStreamDestroy(Cb->own_stream);
-    delete Cb;
-}
-
+extern "C" void selenite_comb_free(selenite_comb *Cb) { pfb_free(Cb); }
 extern "C" int selenite_comb_status(const selenite_comb *Cb) { return Cb ? Cb->status : SELENITE_RX_ARGUMENT_ERROR; }
 extern "C" const char *selenite_comb_error_string(const selenite_comb *Cb) { return Cb ? Cb->err.c_str() : "null combiner"; }
-
-extern "C" int selenite_comb_set_stream(selenite_comb *Cb, void *hip_stream)
-{
-    if (!Cb) return SELENITE_RX_ARGUMENT_ERROR;
-    BCHK(Cb, hipStreamSynchronize(Cb->stream));
-    Cb->stream = hip_stream ? (hipStream_t)hip_stream : Cb->own_stream;
-    return SELENITE_RX_SUCCESS;
-}
-
-extern "C" int selenite_comb_sync(selenite_comb *Cb)
-{
-    if (!Cb) return SELENITE_RX_ARGUMENT_ERROR;
-    BCHK(Cb, hipStreamSynchronize(Cb->stream));
-    return Cb->status;
-}
-
-extern "C" int selenite_comb_reset(selenite_comb *Cb)
-{
-    if (!Cb) return SELENITE_RX_ARGUMENT_ERROR;
-    return reset(Cb);
-}
-
+extern "C" int selenite_comb_set_stream(selenite_comb *Cb, void *hip_stream) { return pfb_set_stream(Cb, hip_stream); }
+extern "C" int selenite_comb_sync(selenite_comb *Cb) { return pfb_sync(Cb); }
+extern "C" int selenite_comb_reset(selenite_comb *Cb) { return Cb ? pfb_reset(Cb) : SELENITE_RX_ARGUMENT_ERROR; }
 extern "C" int selenite_comb_get_state(selenite_comb *Cb, const selenite_comb_state_view *v)
 {
-    if (!Cb || !v) return SELENITE_RX_ARGUMENT_ERROR;
-    BCHK(Cb, hipSetDevice(Cb->device));
-    BCHK(Cb, hipStreamSynchronize(Cb->stream));
-    if (v->history) BCHK(Cb, hipMemcpy(v->history, Cb->d_hist[Cb->cur], Cb->hist_bytes(), hipMemcpyDeviceToHost));
-    if (v->position) *v->position = Cb->position;
-    return SELENITE_RX_SUCCESS;
+    return pfb_state_copy(Cb, v, true, "selenite_comb_get_state");
 }
-
 extern "C" int selenite_comb_set_state(selenite_comb *Cb, const selenite_comb_state_view *v)
 {
-    if (!Cb || !v) return SELENITE_RX_ARGUMENT_ERROR;
-    if (v->position && *v->position % Cb->D() != 0)
-        return fail(Cb, SELENITE_RX_ARGUMENT_ERROR, "selenite_comb_set_state: position is not a multiple of fft_len / oversample");
-    BCHK(Cb, hipSetDevice(Cb->device));
-    BCHK(Cb, hipStreamSynchronize(Cb->stream));
-    if (v->history) BCHK(Cb, hipMemcpy(Cb->d_hist[Cb->cur], v->history, Cb->hist_bytes(), hipMemcpyHostToDevice));
-    if (v->position) Cb->position = *v->position;
-    return SELENITE_RX_SUCCESS;
+    return pfb_state_copy(Cb, v, false, "selenite_comb_set_state");
 }
 
 extern "C" uint32_t selenite_comb_in_channels(const selenite_comb *Cb) { return Cb ? Cb->bands * Cb->n_bins : 0; }

@@ -7,37 +7,22 @@
 // and the row is either that power or row + alpha * (p - row), stored display-ordered (bin k at (k + N / 2) mod N).
 //
 // Every operation of the reference is kept, in its order, and the unit is compiled with -ffp-contract=off and IEEE denormals: bit-exact in
-// every arith mode.  The reference has two butterfly forms: the j = 0 column of a pass and the whole last pass store the sums as they are
-// (:72-135), the other columns multiply them by the twiddles (:143-281).  Both compute the same sums in the same order, so one function
-// serves both and the lanes of column 0 skip the multiplies (1 * x + 0 * y is not x for Inf, NaN and the sign of zero).
+// every arith mode.  The transform, its lane layout and its LDS exchanges are fft8_passes (rx_fft8.h).
 //
-// One single-wave workgroup per channel; no two wavefronts touch one channel's state.  A radix-8 pass of 512 points is 64 butterflies, one
-// per lane:
-//   pass 1  lane j owns elements j + 64 m: eight 512-byte wave loads (256 bytes for int16 slots) put them straight into registers, the window
-//           multiply and the butterfly run there -- no LDS in front of pass 1;
-//   pass 2  lane 8 g + j owns 64 g + j + 8 m: exchanged through LDS at index e + 8 (e >> 6): the eight groups of a wave would otherwise sit
-//           512 bytes apart, on the same banks;
-//   pass 3  lane b owns 8 b + m: exchanged at index e + (e >> 3) (stride 9 instead of 8 between lanes).
-// Both exchanges are conflict-free in writes and reads (64-bit accesses, 32 lanes per LDS cycle covering the 64 banks once).
-// N = 64 is passes 2 and 3 alone with eight frames per wave (lane 8 f + j owns elements j + 8 m of frame slot f; the slots are consecutive
-// TRANSFORMED frames, so a stride leaves no lane idle); their powers go through LDS to lane k = display index, which averages them in order.
+// One single-wave workgroup per channel; no two wavefronts touch one channel's state.  N = 512: lane j loads elements j + 64 m with eight
+// 512-byte wave loads (256 bytes for int16 slots) straight into registers, where the window multiply runs.  N = 64: eight frames per wave
+// (lane 8 f + j owns elements j + 8 m of frame slot f; the slots are consecutive TRANSFORMED frames, so a stride leaves no lane idle); their
+// powers go through LDS to lane k = display index, which averages them in order.
 // The row lives in registers across the frames of a call: read once (averaging only) and written once per call.  The pending frame is read
 // only by a call that starts inside a transformed frame and written only by one that ends inside one; skipped frames are never read.
 #include "rx_host.h"
-#include "rx_fft8.h"       // spec_twiddles, bfly8, twiddle7: shared with chan.hip
+#include "rx_fft8.h"       // spec_twiddles, fft8_twiddles, fft8_passes
 
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
 namespace srx {
-
-__device__ __forceinline__ float2 spec_load(const float *x, int64_t v) { return reinterpret_cast<const float2 *>(x)[v]; }
-__device__ __forceinline__ float2 spec_load(const int16_t *x, int64_t v)
-{
-    const short2 s = reinterpret_cast<const short2 *>(x)[v];
-    return make_float2(q15_to_float(s.x), q15_to_float(s.y));      // arm_q15_to_float
-}
 
 template <int N, typename TIn>
 __global__ __launch_bounds__(64) void k_spectrum(SpecParams q, const TIn *__restrict__ src)
@@ -56,7 +41,7 @@ __global__ __launch_bounds__(64) void k_spectrum(SpecParams q, const TIn *__rest
     const uint32_t ne = nfr > q.first ? (nfr - 1u - q.first) / q.stride + 1u : 0u;
     auto elem = [&](int64_t v) -> float2 {
         if (v < 0) return reinterpret_cast<const float2 *>(pend)[v + off];
-        return spec_load(x, v);
+        return load_iq(x, v);
     };
 
     if (ne) {
@@ -66,12 +51,7 @@ __global__ __launch_bounds__(64) void k_spectrum(SpecParams q, const TIn *__rest
         float2 tw1[7], tw2[7];
 #pragma unroll
         for (int m = 0; m < 8; ++m) w[m] = q.window ? q.window[e0 + es * m] : 1.0f;
-#pragma unroll
-        for (int k = 1; k < 8; ++k) {
-            // pass n2 = 64 (twidCoefModifier 1): ia_k = k * j; pass n2 = 8 (modifier N / 64): ia_k = k * j * N / 64 (:146-168)
-            if (N == 512) tw1[k - 1] = reinterpret_cast<const float2 *>(q.tw)[k * lane];
-            tw2[k - 1] = reinterpret_cast<const float2 *>(q.tw)[(N / 64) * k * j2];
-        }
+        fft8_twiddles<N>(q.tw, lane, tw1, tw2);
         // display index of power m of this lane: N = 512: position 8 * lane + m = digits (g, j2, m) holds bin 64 m + 8 j2 + g;
         // N = 64: position 8 * j2 + m of the lane's frame holds bin 8 m + j2 (arm_bitreversal_32 with armBitRevIndexTableN: base-8 digit reversal)
         const uint32_t dlo = N == 512 ? 8u * j2 + g : j2, dst = N == 512 ? 64u : 8u;
@@ -97,25 +77,7 @@ __global__ __launch_bounds__(64) void k_spectrum(SpecParams q, const TIn *__rest
 #pragma unroll
                 for (int m = 0; m < 8; ++m) a[m] = make_float2(a[m].x * w[m], a[m].y * w[m]);
             }
-            if (N == 512) {
-                bfly8(a);
-                if (lane != 0u) twiddle7(a, tw1);
-                __syncthreads();                             // (one wave: orders the LDS traffic across lanes for the compiler)
-#pragma unroll
-                for (int m = 0; m < 8; ++m) fs[lane + 72u * m] = a[m];
-                __syncthreads();
-#pragma unroll
-                for (int m = 0; m < 8; ++m) a[m] = fs[72u * g + j2 + 8u * m];
-            }
-            bfly8(a);
-            if (j2 != 0u) twiddle7(a, tw2);
-            __syncthreads();
-#pragma unroll
-            for (int m = 0; m < 8; ++m) fs[72u * g + j2 + 9u * m] = a[m];
-            __syncthreads();
-#pragma unroll
-            for (int m = 0; m < 8; ++m) a[m] = fs[9u * lane + m];
-            bfly8(a);                                        // n2 = 1: every butterfly is of the twiddle-free form
+            fft8_passes<N>(a, tw1, tw2, fs, lane);
 
             float p[8];
 #pragma unroll
@@ -161,7 +123,7 @@ __global__ __launch_bounds__(64) void k_spectrum(SpecParams q, const TIn *__rest
     // the frame the call ends in, when it will be transformed: its samples so far wait in pending (those of earlier calls stay where they are)
     const int64_t vt = (int64_t)nfr * N - off;
     if (vt < L && nfr >= q.first && (nfr - q.first) % q.stride == 0u)
-        for (int64_t v = (vt > 0 ? vt : 0) + lane; v < L; v += kWave) reinterpret_cast<float2 *>(pend)[v - vt] = spec_load(x, v);
+        for (int64_t v = (vt > 0 ? vt : 0) + lane; v < L; v += kWave) reinterpret_cast<float2 *>(pend)[v - vt] = load_iq(x, v);
 }
 
 hipError_t launch_spectrum(const SpecParams &q, uint32_t fft_len, const void *src, bool src_q15, hipStream_t st)

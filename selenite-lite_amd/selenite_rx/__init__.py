@@ -1523,81 +1523,78 @@ def design_chan_prototype(fft_len, taps_per_branch, width=1.0):
     return g
 
 
-class Channelizer:
-    """One selenite_chan object (include/selenite_chan.h): `bands` wideband I/Q streams in, bands * n_bins channels out, in the layout
-    Rx.process_device reads.  Device pointers only (DeviceBuffer.ptr)."""
+class _FilterBank:
+    """What Channelizer and Combiner share: one object of the C prefix `_prefix` (selenite_chan_ / selenite_comb_) whose state is a history
+    of shape _hist_shape() and a position.  Device pointers only (DeviceBuffer.ptr)."""
+    _prefix = None
+    _config = None
+    _state_view = None
 
-    def __init__(self, bands, fft_len, oversample, taps_per_branch, coeffs, bins=None):
+    def _init(self, bands, fft_len, oversample, taps_per_branch, coeffs, bins, *own_fields):
         self.L = lib()
         coeffs = np.ascontiguousarray(coeffs, np.float32)
         assert coeffs.size == fft_len * taps_per_branch, coeffs.shape
         b = None if bins is None else np.ascontiguousarray(bins, np.uint32)
         self.bands, self.fft_len, self.oversample, self.taps_per_branch = int(bands), int(fft_len), int(oversample), int(taps_per_branch)
         self.n_bins = self.fft_len if b is None else int(b.size)
-        cfg = ChanConfig(C.sizeof(ChanConfig), self.bands, self.fft_len, self.oversample, self.taps_per_branch, self.n_bins, 0, _fp(coeffs),
-                         None if b is None else b.ctypes.data_as(u32p))
+        cfg = self._config(C.sizeof(self._config), self.bands, self.fft_len, self.oversample, self.taps_per_branch, self.n_bins, *own_fields, 0,
+                           _fp(coeffs), None if b is None else b.ctypes.data_as(u32p))
         self.h = C.c_void_p()
-        rc = self.L.selenite_chan_init(C.byref(self.h), C.byref(cfg))
+        rc = self._c("init")(C.byref(self.h), C.byref(cfg))
         if rc:
-            raise RxError(rc, "selenite_chan_init failed (no GPU, or a bad configuration)")
-        self.decim = self.fft_len // self.oversample
-        self.hist_len = self.fft_len * self.taps_per_branch - self.decim
+            raise RxError(rc, "%sinit failed (no GPU, or a bad configuration)" % self._prefix)
+
+    def _c(self, name):
+        return getattr(self.L, self._prefix + name)
+
+    def _raise(self, rc):
+        if rc:
+            raise RxError(rc, self._c("error_string")(self.h).decode())
 
     def status(self):
-        return self.L.selenite_chan_status(self.h)
+        return self._c("status")(self.h)
 
     def check(self):
-        rc = self.L.selenite_chan_status(self.h)
-        if rc:
-            raise RxError(rc, self.L.selenite_chan_error_string(self.h).decode())
-
-    def out_channels(self):
-        return self.L.selenite_chan_out_channels(self.h)
+        self._raise(self.status())
 
     def out_len(self, block_size):
-        return self.L.selenite_chan_out_len(self.h, block_size)
+        return self._c("out_len")(self.h, block_size)
 
     def process_device(self, d_src, d_dst, block_size):
-        """d_src [bands][block_size][2] f32 -> d_dst [bands * n_bins][block_size / D][2] f32, asynchronous; a refused call raises"""
-        self.L.selenite_chan_process_f32_device(self.h, d_src, d_dst, block_size)
+        """f32 in, f32 out, asynchronous; a refused call raises"""
+        self._c("process_f32_device")(self.h, d_src, d_dst, block_size)
         self.check()
 
     def process_q15_device(self, d_src, d_dst, block_size):
-        """int16 input (arm_q15_to_float), f32 output"""
-        self.L.selenite_chan_process_q15_device(self.h, d_src, d_dst, block_size)
+        """the int16 side of the object (Channelizer: the input; Combiner: the output)"""
+        self._c("process_q15_device")(self.h, d_src, d_dst, block_size)
         self.check()
 
     def set_stream(self, stream_ptr):
-        return self.L.selenite_chan_set_stream(self.h, stream_ptr)
+        return self._c("set_stream")(self.h, stream_ptr)
 
     def sync(self):
-        rc = self.L.selenite_chan_sync(self.h)
-        if rc:
-            raise RxError(rc, self.L.selenite_chan_error_string(self.h).decode())
+        self._raise(self._c("sync")(self.h))
 
     def reset(self):
-        return self.L.selenite_chan_reset(self.h)
+        return self._c("reset")(self.h)
 
     def state(self):
-        a = {"history": np.zeros((self.bands, self.hist_len, 2), np.float32), "position": np.zeros(1, np.uint64)}
-        v = ChanStateView(_fp(a["history"]), a["position"].ctypes.data_as(u64p))
-        rc = self.L.selenite_chan_get_state(self.h, C.byref(v))
-        if rc:
-            raise RxError(rc, self.L.selenite_chan_error_string(self.h).decode())
+        a = {"history": np.zeros(self._hist_shape(), np.float32), "position": np.zeros(1, np.uint64)}
+        v = self._state_view(_fp(a["history"]), a["position"].ctypes.data_as(u64p))
+        self._raise(self._c("get_state")(self.h, C.byref(v)))
         return a
 
     def set_state(self, a):
         hist = np.ascontiguousarray(a["history"], np.float32) if a.get("history") is not None else None
         pos = np.ascontiguousarray(a["position"], np.uint64) if a.get("position") is not None else None
-        assert hist is None or hist.shape == (self.bands, self.hist_len, 2), hist.shape
-        v = ChanStateView(None if hist is None else _fp(hist), None if pos is None else pos.ctypes.data_as(u64p))
-        rc = self.L.selenite_chan_set_state(self.h, C.byref(v))
-        if rc:
-            raise RxError(rc, self.L.selenite_chan_error_string(self.h).decode())
+        assert hist is None or hist.shape == self._hist_shape(), hist.shape
+        v = self._state_view(None if hist is None else _fp(hist), None if pos is None else pos.ctypes.data_as(u64p))
+        self._raise(self._c("set_state")(self.h, C.byref(v)))
 
     def close(self):
         if self.h:
-            self.L.selenite_chan_free(self.h)
+            self._c("free")(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):
@@ -1605,6 +1602,24 @@ class Channelizer:
             self.close()
         except Exception:
             pass
+
+
+class Channelizer(_FilterBank):
+    """One selenite_chan object (include/selenite_chan.h): `bands` wideband I/Q streams in, bands * n_bins channels out, in the layout
+    Rx.process_device reads: d_src [bands][block_size][2] f32 (process_q15_device: int16, arm_q15_to_float) -> d_dst
+    [bands * n_bins][block_size / D][2] f32."""
+    _prefix, _config, _state_view = "selenite_chan_", ChanConfig, ChanStateView
+
+    def __init__(self, bands, fft_len, oversample, taps_per_branch, coeffs, bins=None):
+        self._init(bands, fft_len, oversample, taps_per_branch, coeffs, bins)
+        self.decim = self.fft_len // self.oversample
+        self.hist_len = self.fft_len * self.taps_per_branch - self.decim
+
+    def _hist_shape(self):
+        return (self.bands, self.hist_len, 2)
+
+    def out_channels(self):
+        return self._c("out_channels")(self.h)
 
 
 def design_comb_prototype(fft_len, taps_per_branch, width=1.0, oversample=1):
@@ -1617,85 +1632,19 @@ def design_comb_prototype(fft_len, taps_per_branch, width=1.0, oversample=1):
     return g
 
 
-class Combiner:
+class Combiner(_FilterBank):
     """One selenite_comb object (include/selenite_comb.h): bands * n_bins TX channel rows in, in the layout Tx.process_device writes, `bands`
-    wideband I/Q streams out, f32 or int16.  Device pointers only (DeviceBuffer.ptr)."""
+    wideband I/Q streams out: d_src [bands * n_bins][block_size][2] f32 -> d_dst [bands][block_size * D][2] f32 (process_q15_device: int16,
+    arm_float_to_q15, saturating)."""
+    _prefix, _config, _state_view = "selenite_comb_", CombConfig, CombStateView
 
     def __init__(self, bands, fft_len, oversample, taps_per_branch, coeffs, bins=None, q15_rounding=0):
-        self.L = lib()
-        coeffs = np.ascontiguousarray(coeffs, np.float32)
-        assert coeffs.size == fft_len * taps_per_branch, coeffs.shape
-        b = None if bins is None else np.ascontiguousarray(bins, np.uint32)
-        self.bands, self.fft_len, self.oversample, self.taps_per_branch = int(bands), int(fft_len), int(oversample), int(taps_per_branch)
-        self.n_bins = self.fft_len if b is None else int(b.size)
-        cfg = CombConfig(C.sizeof(CombConfig), self.bands, self.fft_len, self.oversample, self.taps_per_branch, self.n_bins, int(q15_rounding), 0,
-                         _fp(coeffs), None if b is None else b.ctypes.data_as(u32p))
-        self.h = C.c_void_p()
-        rc = self.L.selenite_comb_init(C.byref(self.h), C.byref(cfg))
-        if rc:
-            raise RxError(rc, "selenite_comb_init failed (no GPU, or a bad configuration)")
+        self._init(bands, fft_len, oversample, taps_per_branch, coeffs, bins, int(q15_rounding))
         self.interp = self.fft_len // self.oversample
         self.hist_len = self.taps_per_branch * self.oversample - 1
 
-    def status(self):
-        return self.L.selenite_comb_status(self.h)
-
-    def check(self):
-        rc = self.L.selenite_comb_status(self.h)
-        if rc:
-            raise RxError(rc, self.L.selenite_comb_error_string(self.h).decode())
+    def _hist_shape(self):
+        return (self.bands * self.n_bins, self.hist_len, 2)
 
     def in_channels(self):
-        return self.L.selenite_comb_in_channels(self.h)
-
-    def out_len(self, block_size):
-        return self.L.selenite_comb_out_len(self.h, block_size)
-
-    def process_device(self, d_src, d_dst, block_size):
-        """d_src [bands * n_bins][block_size][2] f32 -> d_dst [bands][block_size * D][2] f32, asynchronous; a refused call raises"""
-        self.L.selenite_comb_process_f32_device(self.h, d_src, d_dst, block_size)
-        self.check()
-
-    def process_q15_device(self, d_src, d_dst, block_size):
-        """f32 input, int16 output (arm_float_to_q15, saturating)"""
-        self.L.selenite_comb_process_q15_device(self.h, d_src, d_dst, block_size)
-        self.check()
-
-    def set_stream(self, stream_ptr):
-        return self.L.selenite_comb_set_stream(self.h, stream_ptr)
-
-    def sync(self):
-        rc = self.L.selenite_comb_sync(self.h)
-        if rc:
-            raise RxError(rc, self.L.selenite_comb_error_string(self.h).decode())
-
-    def reset(self):
-        return self.L.selenite_comb_reset(self.h)
-
-    def state(self):
-        a = {"history": np.zeros((self.bands * self.n_bins, self.hist_len, 2), np.float32), "position": np.zeros(1, np.uint64)}
-        v = CombStateView(_fp(a["history"]), a["position"].ctypes.data_as(u64p))
-        rc = self.L.selenite_comb_get_state(self.h, C.byref(v))
-        if rc:
-            raise RxError(rc, self.L.selenite_comb_error_string(self.h).decode())
-        return a
-
-    def set_state(self, a):
-        hist = np.ascontiguousarray(a["history"], np.float32) if a.get("history") is not None else None
-        pos = np.ascontiguousarray(a["position"], np.uint64) if a.get("position") is not None else None
-        assert hist is None or hist.shape == (self.bands * self.n_bins, self.hist_len, 2), hist.shape
-        v = CombStateView(None if hist is None else _fp(hist), None if pos is None else pos.ctypes.data_as(u64p))
-        rc = self.L.selenite_comb_set_state(self.h, C.byref(v))
-        if rc:
-            raise RxError(rc, self.L.selenite_comb_error_string(self.h).decode())
-
-    def close(self):
-        if self.h:
-            self.L.selenite_comb_free(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._c("in_channels")(self.h)

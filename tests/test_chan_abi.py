@@ -92,6 +92,45 @@ def test_each_bad_field_returns_its_code(field, value, code):
     assert rc_ == code and h.value is None
 
 
+def apply_faults(cfg, keep, faults):
+    """a field name sets that field; the other names damage what the pointers lead to"""
+    for name, value in faults:
+        if name == "tap":
+            keep[0][-1] = value
+        elif name == "bin":
+            keep[1][1] = value
+        elif name in ("coeffs", "bins"):
+            setattr(cfg, name, None)
+        else:
+            setattr(cfg, name, value)
+
+
+# Two faults at once: which return code wins.  The codes are those the build before the shared filter-bank host code (pfb.h) returned, recorded
+# by running this table against it; none of them is a device error, with or without a GPU.
+PRECEDENCE = [((("fft_len", 128), ("bands", 0)), sr.LENGTH_ERROR),
+              ((("fft_len", 0), ("struct_size", 8)), sr.ARGUMENT_ERROR),
+              ((("tap", np.nan), ("bin", 64)), sr.ARGUMENT_ERROR),
+              ((("reserved", 1), ("coeffs", None)), sr.ARGUMENT_ERROR),
+              ((("bands", 1 << 26), ("n_bins", 0)), sr.ARGUMENT_ERROR),
+              ((("fft_len", 128), ("reserved", 1)), sr.LENGTH_ERROR),
+              ((("fft_len", 128), ("coeffs", None)), sr.LENGTH_ERROR),
+              ((("fft_len", 100), ("oversample", 3)), sr.LENGTH_ERROR),
+              ((("fft_len", 128), ("taps_per_branch", 5)), sr.LENGTH_ERROR),
+              ((("fft_len", 128), ("bins", None)), sr.LENGTH_ERROR),
+              ((("fft_len", 128), ("bands", 1 << 26)), sr.LENGTH_ERROR),
+              ((("struct_size", 0), ("coeffs", None)), sr.ARGUMENT_ERROR),
+              ((("oversample", 0), ("bin", 64)), sr.ARGUMENT_ERROR),
+              ((("bins", None), ("tap", np.inf)), sr.ARGUMENT_ERROR)]
+
+
+@pytest.mark.parametrize("faults,code", PRECEDENCE, ids=["+".join(n for n, _ in f) for f, _ in PRECEDENCE])
+def test_return_code_precedence_of_two_faults(faults, code):
+    cfg, keep = good()
+    apply_faults(cfg, keep, faults)
+    rc_, h = init(cfg)
+    assert rc_ == code and h.value is None
+
+
 def test_bad_pointers_taps_and_bins_are_argument_errors():
     assert sr.lib().selenite_chan_init(None, None) == sr.ARGUMENT_ERROR
     rc_, h = init(None)
