@@ -15,6 +15,17 @@
  *         -> NCO up-mix: out = z * (cos x, +sin x), x from the RX chain's integer phase rule
  *            (arm_sin_f32 / arm_cos_f32 + arm_cmplx_mult_cmplx_f32)
  *
+ * SELENITE_MODE_FM (after selenite_tx_set_fm; DESIGN.md section 2 "TX FM") keeps the front of that chain on one rail and replaces
+ * the up-mix by the phase accumulator itself:
+ *
+ *   audio -> ALC -> arm_fir_f32 (delay taps) => I' (pre-emphasis and the speech band-pass live in these taps; Q' unused, z = (I', +0.0f))
+ *         -> arm_fir_interpolate_f32 by L => u[n]
+ *         -> tone on: w = u[n] + arm_sin_f32(tone phase) * tone_level            (arm_scale_f32, arm_add_f32; CTCSS encoder)
+ *         -> d = arm_float_to_q31(w * deviation)                                 (arm_scale_f32; SupportFunctions/arm_float_to_q31.c)
+ *         -> nco_phase += d;  out = (arm_cos_f32 x, arm_sin_f32 x) * amplitude;  nco_phase += nco_enable ? nco_step : 0
+ *
+ * One 32-bit integer sum modulates and up-mixes: bit-exact however a stream is cut into calls (k_tx_fm, csrc/tx_fm.hip).
+ *
  * Shapes: pSrcAudio [channels][blockSize] (float or q15), pDstIQ [channels][blockSize*interp][2].
  * blockSize counts AUDIO samples and must be a multiple of cfg.block (the ALC block).
  * Status codes, mode bytes and arithmetic modes are selenite_rx.h's: SELENITE_ARITH_CMSIS (bit-exact), _FMA (bit-exact vs the
@@ -48,7 +59,7 @@ typedef struct {
                                   otherwise ARM_MATH_LENGTH_ERROR) */
     uint32_t nh_taps;          /* Hilbert / delay taps (0: Q' = 0, I' = audio) */
     uint8_t  arith;            /* SELENITE_ARITH_* */
-    uint8_t  mode;             /* SELENITE_MODE_* (FM: ARGUMENT_ERROR) */
+    uint8_t  mode;             /* SELENITE_MODE_* (FM: ARGUMENT_ERROR here -- selenite_tx_set_fm, then selenite_tx_set_mode) */
     uint8_t  nco_enable;
     uint8_t  alc_enable;
     uint32_t nco_step_all;     /* phase increment per OUTPUT sample when nco_step is NULL */
@@ -72,9 +83,10 @@ typedef struct {
 
 int  selenite_tx_init(selenite_tx_instance **S, const selenite_tx_config *cfg);
 void selenite_tx_free(selenite_tx_instance *S);
-int  selenite_tx_set_mode(selenite_tx_instance *S, uint8_t mode);     /* DSP_Set_Mode, dsp_if.c:367-370 */
+int  selenite_tx_set_mode(selenite_tx_instance *S, uint8_t mode);     /* DSP_Set_Mode, dsp_if.c:367-370; SELENITE_MODE_FM: ARGUMENT_ERROR (mode kept) until selenite_tx_set_fm */
 int  selenite_tx_status(const selenite_tx_instance *S);
-/* which kernel serves calls whose blockSize is a multiple of 256: "k_tx_fused<4,256,63>" or "k_tx_generic" */
+/* which kernel serves calls whose blockSize is a multiple of 256: "k_tx_fused<4,256,63>", "k_tx_split16<4,256,63>" or "k_tx_generic";
+ * "k_tx_fm" while the mode is SELENITE_MODE_FM */
 const char *selenite_tx_kernel_name(const selenite_tx_instance *S);
 const char *selenite_tx_error_string(const selenite_tx_instance *S);
 
@@ -97,4 +109,8 @@ int  selenite_tx_time_process_device(selenite_tx_instance *S, const float *dSrcA
 #ifdef __cplusplus
 }
 #endif
+
+/* the FM transmit mode with its CTCSS tone encoder: selenite_tx_set_fm and what goes with it */
+#include "selenite_tx_fm.h"
+
 #endif /* SELENITE_TX_H */

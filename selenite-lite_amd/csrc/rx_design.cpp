@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/selenite_rx.h"
+#include "../../include/selenite_tx.h"
 
 static const double kPi = 3.14159265358979323846;
 
@@ -157,4 +158,15 @@ extern "C" uint32_t selenite_rx_ctcss_hz(double hz[50])
     if (hz)
         for (int k = 0; k < 50; ++k) hz[k] = kCtcss[k];
     return 50u;
+}
+
+// include/selenite_tx.h: the phase increment per output sample of a tone of `hz` at the output rate `fs_out`, for
+// selenite_tx_fm_config::tone_step (and nco_step): round(hz / fs_out * 2^32) in double, rounded once, modulo 2^32 (a negative
+// frequency is its two's complement); 0 for arguments that are not finite or a rate that is not positive
+extern "C" uint32_t selenite_tx_tone_step(double hz, double fs_out)
+{
+    if (!std::isfinite(hz) || !std::isfinite(fs_out) || !(fs_out > 0.0)) return 0u;
+    const double turns = hz / fs_out;
+    const double frac = turns - std::floor(turns);          // [0, 1): the step is periodic in whole turns
+    return (uint32_t)((uint64_t)std::llround(frac * 4294967296.0) & 0xFFFFFFFFull);
 }

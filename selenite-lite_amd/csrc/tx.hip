@@ -35,6 +35,10 @@ struct selenite_tx_instance {
     size_t lo_bytes = 0;
     void *d_ttab16 = nullptr;     // k_tx_split16: Toeplitz fragments of the interpolator phases
     int tpost = 0;                // tap scale exponent of that table
+    // SELENITE_MODE_FM (selenite_tx_set_fm, tx_fm.hip)
+    bool fm_set = false;
+    srx::TxFmParams fm{};         // d_tone_step / d_tone_phase live as long as the instance once allocated
+    uint32_t *d_tone_step = nullptr, *d_tone_phase = nullptr;
     hipStream_t stream = nullptr, own_stream = nullptr;
     int status = 0;
     std::string err;
@@ -276,6 +280,14 @@ int run(selenite_tx_instance *S, const void *src, void *dst, bool q15, uint32_t 
     TCHK(S, hipSetDevice(S->device));
     const selenite_tx_config &g = S->cfg;
     const TxParams p = make_params(S, bs);
+    if (g.mode == SELENITE_MODE_FM) {
+        // the phase accumulator carries the modulation: every channel's phase is its own from here on (no shared LO until
+        // reset or set_state say otherwise)
+        S->phase_uniform = false;
+        if (tx_fm_lds_bytes(p) > 64 * 1024) return fail(S, SELENITE_RX_LENGTH_ERROR, "filter lengths exceed the LDS budget of the TX kernel");
+        TCHK(S, launch_tx_fm(p, S->fm, (int)g.arith, src, q15, dst, S->stream));
+        return 0;
+    }
     const uint32_t phase_now = S->phase_host;
     if (g.nco_enable) S->phase_host += bs * g.interp * S->h_step[0];
     if (!S->force_generic && tx_fused_ok(g, S->delay_is_impulse, S->hilb_odd_only, bs)) {
@@ -328,6 +340,7 @@ int reset_state(selenite_tx_instance *S)
     if (nh1) TCHK(S, hipMemsetAsync(S->d_fir_state, 0, C * 2 * nh1 * sizeof(float), S->stream));
     if (p1) TCHK(S, hipMemsetAsync(S->d_int_state, 0, C * 2 * p1 * sizeof(float), S->stream));
     TCHK(S, hipMemsetAsync(S->d_phase, 0, C * sizeof(uint32_t), S->stream));
+    if (S->d_tone_phase) TCHK(S, hipMemsetAsync(S->d_tone_phase, 0, C * sizeof(uint32_t), S->stream));
     std::vector<float> gi(C, g.alc_gain_init);
     TCHK(S, hipMemcpyAsync(S->d_gain, gi.data(), C * sizeof(float), hipMemcpyHostToDevice, S->stream));
     TCHK(S, hipStreamSynchronize(S->stream));
@@ -448,7 +461,7 @@ extern "C" void selenite_tx_free(selenite_tx_instance *S)
 {
     if (!S) return;
     void *ptrs[] = { S->d_ic, S->d_hc, S->d_dc, S->d_sintab, S->d_step, S->d_phase, S->d_fir_state, S->d_int_state,
-                     S->d_gain, S->d_io_in, S->d_io_out, S->d_lo, S->d_ttab16 };
+                     S->d_gain, S->d_io_in, S->d_io_out, S->d_lo, S->d_ttab16, S->d_tone_step, S->d_tone_phase };
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (S->own_stream) (void)hipStreamDestroy(S->own_stream);
@@ -457,7 +470,8 @@ extern "C" void selenite_tx_free(selenite_tx_instance *S)
 
 extern "C" int selenite_tx_set_mode(selenite_tx_instance *S, uint8_t mode)
 {
-    if (!S || !tx_mode_ok(mode)) return SELENITE_RX_ARGUMENT_ERROR;     // instance stays usable in its old mode
+    // instance stays usable in its old mode; FM exists once selenite_tx_set_fm has configured it
+    if (!S || !(tx_mode_ok(mode) || (mode == SELENITE_MODE_FM && S->fm_set))) return SELENITE_RX_ARGUMENT_ERROR;
     S->cfg.mode = mode;
     return SELENITE_RX_SUCCESS;
 }
@@ -465,6 +479,7 @@ extern "C" int selenite_tx_set_mode(selenite_tx_instance *S, uint8_t mode)
 extern "C" const char *selenite_tx_kernel_name(const selenite_tx_instance *S)
 {
     if (!S) return "";
+    if (S->cfg.mode == SELENITE_MODE_FM) return "k_tx_fm";
     if (S->force_generic || !tx_fused_ok(S->cfg, S->delay_is_impulse, S->hilb_odd_only, 256)) return "k_tx_generic";
     return (S->cfg.arith == SELENITE_ARITH_SPLIT16 && S->d_ttab16) ? "k_tx_split16<4,256,63>" : "k_tx_fused<4,256,63>";
 }
@@ -536,6 +551,48 @@ extern "C" int selenite_tx_set_state(selenite_tx_instance *S, const selenite_tx_
         S->phase_uniform = same;
         S->phase_host = v->nco_phase[0];
     }
+    return 0;
+}
+
+extern "C" int selenite_tx_set_fm(selenite_tx_instance *S, const selenite_tx_fm_config *f)
+{
+    if (!S) return SELENITE_RX_ARGUMENT_ERROR;
+    static_assert(sizeof(selenite_tx_fm_config) == 40 && offsetof(selenite_tx_fm_config, tone_step) == 24, "selenite_tx_fm_config layout (LP64)");
+    if (!f) {                                               // FM off again: not from under a running FM mode
+        if (S->cfg.mode == SELENITE_MODE_FM) return SELENITE_RX_ARGUMENT_ERROR;
+        S->fm_set = false;
+        return SELENITE_RX_SUCCESS;
+    }
+    if (f->struct_size != sizeof(selenite_tx_fm_config) || f->reserved != 0 || f->tone_enable > 1u ||
+        !std::isfinite(f->deviation) || !(f->deviation > 0.0f) || !std::isfinite(f->amplitude) || !std::isfinite(f->tone_level))
+        return SELENITE_RX_ARGUMENT_ERROR;                  // the previous setting stays
+    const size_t C = S->cfg.channels;
+    TCHK(S, hipSetDevice(S->device));
+    TCHK(S, hipStreamSynchronize(S->stream));
+    if (!S->d_tone_step) TCHK(S, hipMalloc((void **)&S->d_tone_step, C * sizeof(uint32_t)));
+    if (!S->d_tone_phase) TCHK(S, hipMalloc((void **)&S->d_tone_phase, C * sizeof(uint32_t)));
+    std::vector<uint32_t> ts(C);
+    for (size_t c = 0; c < C; ++c) ts[c] = f->tone_step ? f->tone_step[c] : f->tone_step_all;
+    TCHK(S, hipMemcpy(S->d_tone_step, ts.data(), C * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!S->fm_set) TCHK(S, hipMemset(S->d_tone_phase, 0, C * sizeof(uint32_t)));     // a retune keeps the tone's phase
+    S->fm = srx::TxFmParams{ f->deviation, f->amplitude, f->tone_level, f->tone_enable, S->d_tone_step, S->d_tone_phase };
+    S->fm_set = true;
+    return SELENITE_RX_SUCCESS;
+}
+
+extern "C" int selenite_tx_get_fm_state(selenite_tx_instance *S, const selenite_tx_fm_state_view *v)
+{
+    if (!S || !v || !S->fm_set) return SELENITE_RX_ARGUMENT_ERROR;
+    TCHK(S, hipStreamSynchronize(S->stream));
+    if (v->tone_phase) TCHK(S, hipMemcpy(v->tone_phase, S->d_tone_phase, S->cfg.channels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int selenite_tx_set_fm_state(selenite_tx_instance *S, const selenite_tx_fm_state_view *v)
+{
+    if (!S || !v || !S->fm_set) return SELENITE_RX_ARGUMENT_ERROR;
+    TCHK(S, hipStreamSynchronize(S->stream));
+    if (v->tone_phase) TCHK(S, hipMemcpy(S->d_tone_phase, v->tone_phase, S->cfg.channels * sizeof(uint32_t), hipMemcpyHostToDevice));
     return 0;
 }
 

@@ -1,4 +1,4 @@
-// tx_internal.h -- kernel parameter block and launch interfaces shared by tx.hip and tx_fused.hip.
+// tx_internal.h -- kernel parameter block and launch interfaces shared by tx.hip, tx_fused.hip and tx_fm.hip.
 // Not part of the C-ABI (include/selenite_tx.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,5 +33,16 @@ hipError_t launch_tx_fused(const TxParams &p, int arith, uint32_t delay_idx, con
 hipError_t build_tx_split16_table(const float *interp_coeffs, void **d_table, int *tap_sc);
 hipError_t launch_tx_split16(const TxParams &p, uint32_t delay_idx, const float2 *lo, const void *ttab16, int tap_sc,
                              const void *src, bool q15, void *dst, hipStream_t st);
+
+// tx_fm.hip: SELENITE_MODE_FM (selenite_tx_set_fm).  k_tx_fm<ARITH, TIn, TOut>: any shape k_tx_generic serves, one single-wave
+// workgroup per channel; p.phase is read and written whatever p.nco says (the phase accumulator is the modulator)
+struct TxFmParams {
+    float deviation, amplitude, tone_level;
+    uint32_t tone_on;
+    const uint32_t *tone_step;     // [C]
+    uint32_t *tone_phase;          // [C]
+};
+size_t tx_fm_lds_bytes(const TxParams &p);
+hipError_t launch_tx_fm(const TxParams &p, const TxFmParams &f, int arith, const void *src, bool q15, void *dst, hipStream_t st);
 
 }  // namespace srx

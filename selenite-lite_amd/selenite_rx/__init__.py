@@ -195,6 +195,17 @@ class TxStateView(C.Structure):
     _fields_ = [("fir_state", f32p), ("interp_state", f32p), ("alc_gain", f32p), ("nco_phase", u32p)]
 
 
+class TxFmConfig(C.Structure):
+    """struct selenite_tx_fm_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("deviation", C.c_float), ("amplitude", C.c_float), ("tone_enable", C.c_uint32),
+                ("tone_level", C.c_float), ("tone_step_all", C.c_uint32), ("tone_step", u32p), ("reserved", C.c_uint32)]
+
+
+class TxFmStateView(C.Structure):
+    """struct selenite_tx_fm_state_view."""
+    _fields_ = [("tone_phase", u32p)]
+
+
 # every symbol include/selenite_tx.h declares
 TX_ABI_SYMBOLS = [
     "selenite_tx_init", "selenite_tx_free", "selenite_tx_set_mode", "selenite_tx_status", "selenite_tx_error_string",
@@ -203,6 +214,9 @@ TX_ABI_SYMBOLS = [
     "selenite_tx_process_q15_device", "selenite_tx_set_stream", "selenite_tx_sync", "selenite_tx_get_state",
     "selenite_tx_set_state", "selenite_tx_reset", "selenite_tx_time_process_device",
 ]
+
+# every symbol include/selenite_tx_fm.h declares (the FM transmit mode; selenite_tx.h includes it)
+TXFM_ABI_SYMBOLS = ["selenite_tx_set_fm", "selenite_tx_get_fm_state", "selenite_tx_set_fm_state", "selenite_tx_tone_step"]
 
 # every symbol include/selenite_ring.h declares
 RING_ABI_SYMBOLS = [
@@ -385,6 +399,12 @@ def lib():
             L.selenite_rx_design_tones.argtypes = [f32p, C.POINTER(C.c_double), C.c_uint32]
             L.selenite_rx_ctcss_hz.argtypes = [C.POINTER(C.c_double)]
             L.selenite_rx_ctcss_hz.restype = C.c_uint32
+        if hasattr(L, "selenite_tx_set_fm"):                # (an older build named by SELENITE_RX_LIB lacks the FM transmit mode)
+            L.selenite_tx_set_fm.argtypes = [vp, C.POINTER(TxFmConfig)]
+            L.selenite_tx_get_fm_state.argtypes = [vp, C.POINTER(TxFmStateView)]
+            L.selenite_tx_set_fm_state.argtypes = [vp, C.POINTER(TxFmStateView)]
+            L.selenite_tx_tone_step.argtypes = [C.c_double, C.c_double]
+            L.selenite_tx_tone_step.restype = C.c_uint32
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -485,6 +505,11 @@ def ctcss_hz():
     hz = np.zeros(50, np.float64)
     n = lib().selenite_rx_ctcss_hz(hz.ctypes.data_as(C.POINTER(C.c_double)))
     return hz[:n]
+
+
+def tone_step(hz, fs_out):
+    """phase increment per output sample of a tone (Tx.set_fm tone_step, nco_step): round(hz / fs_out * 2^32)"""
+    return int(lib().selenite_tx_tone_step(hz, fs_out))
 
 
 def design_interp(ni_taps, interp, cutoff):
@@ -1494,6 +1519,45 @@ class Tx:
         rc = self.L.selenite_tx_set_state(self.h, C.byref(v))
         if rc:
             raise RxError(rc, self.L.selenite_tx_error_string(self.h).decode())
+
+    def set_fm(self, deviation=0.25, amplitude=1.0, tone_level=0.0, tone_step=None, tone_enable=None):
+        """FM transmit mode (selenite_tx_set_fm; then set_mode(MODE_FM)).  tone_step: None (no tone), one phase increment per output
+        sample for every channel, or an array [channels]; tone_enable defaults to `tone_step is not None`.  Returns the status code."""
+        g = TxFmConfig()
+        g.struct_size, g.deviation, g.amplitude, g.tone_level, g.reserved = C.sizeof(TxFmConfig), deviation, amplitude, tone_level, 0
+        g.tone_enable = int(tone_step is not None) if tone_enable is None else int(tone_enable)
+        steps = None
+        if tone_step is not None and np.ndim(tone_step):
+            steps = np.ascontiguousarray(tone_step, np.uint32)
+            if steps.shape != (self.cfg.channels,):
+                raise ValueError("tone_step: one value or [channels]")
+            g.tone_step = steps.ctypes.data_as(u32p)
+        elif tone_step is not None:
+            g.tone_step_all = int(tone_step)
+        return self.L.selenite_tx_set_fm(self.h, C.byref(g))
+
+    def clear_fm(self):
+        """selenite_tx_set_fm(S, NULL): FM off again (ARGUMENT_ERROR while the mode is FM)"""
+        return self.L.selenite_tx_set_fm(self.h, None)
+
+    def fm_state(self):
+        a = {"tone_phase": np.zeros(self.cfg.channels, np.uint32)}
+        v = TxFmStateView()
+        v.tone_phase = a["tone_phase"].ctypes.data_as(u32p)
+        rc = self.L.selenite_tx_get_fm_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_tx_get_fm_state: FM is not configured (set_fm)")
+        return a
+
+    def set_fm_state(self, a):
+        tp = np.ascontiguousarray(a["tone_phase"], np.uint32)
+        if tp.shape != (self.cfg.channels,):
+            raise ValueError("tone_phase: [channels]")
+        v = TxFmStateView()
+        v.tone_phase = tp.ctypes.data_as(u32p)
+        rc = self.L.selenite_tx_set_fm_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_tx_set_fm_state: FM is not configured (set_fm)")
 
     def time_process(self, d_src, d_dst, block_size, iters):
         ms = C.c_float()
