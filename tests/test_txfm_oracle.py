@@ -1,14 +1,17 @@
 """CPU: the numpy restatement of the TX chain's FM mode (tests/txfm_oracle.py) against the fixture made from the reference's CMSIS-DSP
 functions (tests/golden/txfm.npz, tests/golden/make_txfm_golden.py), and what the mode is for: this chain's own FM demodulator gives the
 modulating signal back, and its tone detector reads the CTCSS tone that was sent."""
+import copy
 import os
 
 import numpy as np
 import pytest
 
+import gain_law_cases as gl
 import rxcommon as rc
 import selenite_rx as sr
 import tones_oracle as to
+import tx_fuzz_cases as fz
 import txfm_oracle as fo
 
 f32 = np.float32
@@ -102,6 +105,98 @@ def test_calls_of_any_cut_give_the_same_output_and_state(arith):
     for y, st in runs[1:]:
         assert rc.identical(y, runs[0][0]) and states_identical(st, runs[0][1])
     assert (runs[0][1]["nco_phase"] != 0).all() and (runs[0][1]["tone_phase"] != 0).all()
+
+
+# ---- the oracle's face for call sequences (tests/test_gpu_tx_fuzz.py), on the fuzz generator's own shapes ----
+PIN_CASES = 40
+
+
+def pin_specs():
+    """the fuzz generator's first 40 specs (taps overwritten as the cases say: moved impulse, odd-distance values, dense FIRs),
+    each with the NCO, q15_rounding and arithmetic the case drew -- SPLIT16 runs as FMA here"""
+    out = []
+    for case in fz.cases(fz.SEED, PIN_CASES // 2, None):
+        if case["kind"] == "FM":
+            continue
+        spec = fz.build_spec(case)
+        if spec.arith == rc.ARITH_SPLIT16:
+            spec.arith = rc.ARITH_FMA
+        if spec.channels > 5:                      # channels are independent streams: five of them, to keep this a quick CPU test
+            spec.channels = 5
+            spec.nco_steps = None if spec.nco_steps is None else spec.nco_steps[:5].copy()
+        out.append((case, spec))
+    assert len(out) == PIN_CASES
+    return out
+
+
+def pin_audio(case, spec, k, q15):
+    a = rc.synth_audio(k, spec.channels, 100 * k, (3 - k) * spec.block)
+    return gl.to_q15(a) if q15 else a
+
+
+def test_pin_specs_cover_both_values_of_every_switch():
+    specs = [s for _, s in pin_specs()]
+    assert {s.nco for s in specs} == {False, True} and {s.q15_rounding for s in specs} == {False, True}
+    assert {s.arith for s in specs} == {rc.ARITH_CMSIS, rc.ARITH_FMA} and {s.alc for s in specs} == {False, True}
+    assert any(s.nco_steps is not None for s in specs) and any(s.interp == 1 for s in specs) and any(s.nh_taps == 0 for s in specs)
+    taps = {c["taps"][k][0] for c, _ in pin_specs() for k in ("delay", "hilb", "ic")}
+    assert taps >= {"designed", "impulse", "odd", "dense"}
+
+
+@pytest.mark.parametrize("mode", fz.MODES)
+def test_every_other_mode_equals_the_tx_oracle_on_bits(mode):
+    """TxFmOracle without an FM setting is rc.TxCpuChain(spec, "orc"): the restated up-mix, the q15 composition and the state, when the
+    mode is the spec's own and when set_mode brings it"""
+    for case, spec in pin_specs():
+        for created_in_mode in (True, False):
+            s = copy.copy(spec)
+            if created_in_mode:
+                s.mode = mode
+            o, t = fo.TxFmOracle(s), rc.TxCpuChain(s, "orc")
+            assert t.ok() and o.set_mode(rc.MODE_FM) == rc.ARGUMENT_ERROR and o.mode == s.mode
+            if not created_in_mode:
+                a = pin_audio(case, s, 2, False)
+                assert rc.identical(o.process(a), t.process(a))
+                assert o.set_mode(mode) == 0 and t.set_mode(mode) == 0
+            for k, q15 in enumerate((False, True)):
+                a = pin_audio(case, s, k, q15)
+                got, want = (o.process_q15(a), t.process_q15(a)) if q15 else (o.process(a), t.process(a))
+                assert rc.identical(got, want), (case, mode, k)
+            so, st = o.state(), t.state()
+            assert not so.pop("tone_phase").any()
+            assert states_identical(so, st), (case, mode)
+
+
+@pytest.mark.parametrize("fm", [False, True])
+def test_reset_equals_a_fresh_oracle_on_bits(fm):
+    tsteps = np.array([0x0B4E81B5, 0x80000001, 0xFFFFFF01], np.uint32)
+    for arith in (rc.ARITH_CMSIS, rc.ARITH_FMA):
+        spec = fm_spec(3, 32, 3, 45, 15, arith, nco_steps=np.array([0x3A5F1C27, 0xC0000001, 0], np.uint32), alc_params=gl.SETS["odd"])
+        used, fresh = (fo.TxFmOracle(spec, 0.7, 0.9, 0.2, tsteps) for _ in range(2))
+        for o in (used, fresh):
+            assert o.set_mode(rc.MODE_FM if fm else rc.MODE_LSB) == 0
+        used.process(rc.synth_audio(0, 3, 0, 96))
+        st = used.state()
+        assert st["nco_phase"].any() and (st["alc_gain"] != f32(gl.SETS["odd"]["gain_init"])).all() and st["tone_phase"].any() == fm
+        assert used.reset() == 0 and used.mode == fresh.mode and used.fm_set
+        assert states_identical(used.state(), fresh.state())
+        a = rc.synth_audio(0, 3, 96, 64)
+        assert rc.identical(used.process(a), fresh.process(a)) and states_identical(used.state(), fresh.state())
+
+
+def test_fm_is_optional_and_the_first_setting_starts_the_tone_at_zero():
+    spec = fm_spec(2, 16, 2, 2, 1)
+    o = fo.TxFmOracle(spec)
+    assert not o.fm_set and o.set_mode(rc.MODE_FM) == rc.ARGUMENT_ERROR and o.mode == rc.MODE_USB
+    assert o.set_fm(0.3, 1.0, 0.1, 0x01234567) == 0 and o.set_mode(rc.MODE_FM) == 0
+    o.process(rc.synth_audio(0, 2, 0, 32))
+    tp = o.state()["tone_phase"]
+    assert tp.all() and o.clear_fm() == rc.ARGUMENT_ERROR and o.fm_set
+    o.set_fm(0.2, 1.0, 0.1, 0x01234567)
+    assert rc.identical(o.state()["tone_phase"], tp), "a retune keeps the tone's phase"
+    assert o.set_mode(rc.MODE_USB) == 0 and o.clear_fm() == 0 and o.set_mode(rc.MODE_FM) == rc.ARGUMENT_ERROR
+    o.set_fm(0.2, 1.0, 0.1, 0x01234567)
+    assert not o.state()["tone_phase"].any()
 
 
 # ---- what the mode is for ---------------------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ arm_add_f32) pins it bit for bit (tests/test_txfm_oracle.py).  The front of the 
 arm_fir_interpolate_f32 -- is the existing oracle's (rc.TxCpuChain over oracle/tx_oracle.c): a USB instance without NCO whose Hilbert taps
 are all +0.0f has the FM instance's I rail and, bit for bit, its fir_state, interp_state and alc_gain.
 
-TxFmOracle follows an instance through mode switches as well.  The two interpolator rails are independent filters, so two oracle instances
+TxFmOracle follows an instance through mode switches, FM settings (set_fm, clear_fm), reset() and a restored phase as well.  The two interpolator rails are independent filters, so two oracle instances
 side by side give every rail of every mode: `b` (Hilbert taps +0.0f; AM while the mode is AM, else USB) the I rail, `a` (the instance's own
 taps; AM while the mode is FM, so that its Q rail takes +0.0f) the Q rail.  The up-mix of the other modes is restated here too
 (arm_cmplx_mult_cmplx_f32.c:186-187), because the phase accumulator is shared with FM.
@@ -128,40 +128,77 @@ def fm_tail_sequential(u, phase, step, deviation, amplitude, tone_phase=0, tone_
 
 
 class TxFmOracle:
-    """A TX instance with the FM mode configured, followed through calls and mode switches (module docstring).
-    spec: the rc.TxSpec the instance was created from; tone_steps: [channels] or None (tone off)."""
+    """A TX instance followed through calls, mode switches, FM settings and resets (module docstring).
+    spec: the rc.TxSpec the instance was created from -- its taps (spec.delay, spec.hilb, spec.ic) are taken as they stand, so a test may
+    overwrite them before it builds the instance and the oracle; deviation: None leaves FM unconfigured (set_mode(MODE_FM) is then refused
+    as selenite_tx_set_mode refuses it); tone_steps: [channels], one value for all, or None (tone off)."""
 
-    def __init__(self, spec, deviation, amplitude=1.0, tone_level=0.0, tone_steps=None):
+    def __init__(self, spec, deviation=None, amplitude=1.0, tone_level=0.0, tone_steps=None):
         self.spec = spec
         C_ = spec.channels
-        sa, sb = copy.copy(spec), copy.copy(spec)
-        sa.nco = sb.nco = False
-        sb.mode = rc.MODE_USB
-        if spec.nh_taps:
-            sb.hilb = np.zeros(spec.nh_taps, f32)
-        self.a, self.b = rc.TxCpuChain(sa, "orc"), rc.TxCpuChain(sb, "orc")
-        assert self.a.ok() and self.b.ok()
         self.mode = spec.mode
+        self._chains()
         self.steps = np.zeros(C_, np.uint32)
         if spec.nco:
             self.steps[:] = spec.nco_steps if spec.nco_steps is not None else spec.nco_step_all
         self.phase = np.zeros(C_, np.uint32)
         self.tone_phase = np.zeros(C_, np.uint32)
-        self.set_fm(deviation, amplitude, tone_level, tone_steps)
+        self.fm_set = False
+        if deviation is not None:
+            self.set_fm(deviation, amplitude, tone_level, tone_steps)
         self.last_d = None
 
+    def _chains(self):
+        """both inner chains new (zero filter state, alc_gain = gain_init) in the current mode"""
+        sa, sb = copy.copy(self.spec), copy.copy(self.spec)
+        sa.nco = sb.nco = False
+        sa.mode = sb.mode = rc.MODE_USB
+        if self.spec.nh_taps:
+            sb.hilb = np.zeros(self.spec.nh_taps, f32)
+        self.a, self.b = rc.TxCpuChain(sa, "orc"), rc.TxCpuChain(sb, "orc")
+        assert self.a.ok() and self.b.ok()
+        self._inner_modes()
+
+    def _inner_modes(self):
+        assert self.a.set_mode(rc.MODE_AM if self.mode == rc.MODE_FM else self.mode) == 0
+        assert self.b.set_mode(rc.MODE_AM if self.mode == rc.MODE_AM else rc.MODE_USB) == 0
+
     def set_fm(self, deviation, amplitude=1.0, tone_level=0.0, tone_steps=None):
-        """a retune: tone_phase stays"""
+        """a retune: tone_phase stays; the first setting (or the first behind clear_fm) starts the tone at phase 0"""
         self.deviation, self.amplitude, self.tone_level = deviation, amplitude, tone_level
         self.tone_on = tone_steps is not None
         self.tone_steps = np.zeros(self.spec.channels, np.uint32)
         if self.tone_on:
             self.tone_steps[:] = tone_steps
+        if not self.fm_set:
+            self.tone_phase[:] = 0
+        self.fm_set = True
+        return 0
+
+    def clear_fm(self):
+        """selenite_tx_set_fm(S, NULL): refused while the mode is FM"""
+        if self.mode == rc.MODE_FM:
+            return rc.ARGUMENT_ERROR
+        self.fm_set = False
+        return 0
+
+    def reset(self):
+        """selenite_tx_reset: filter states, gains and both phases as in a new instance; the mode and the FM setting stay"""
+        self._chains()
+        self.phase[:] = 0
+        self.tone_phase[:] = 0
+        return 0
+
+    def set_phase(self, phase):
+        """selenite_tx_set_state with nco_phase alone changed"""
+        self.phase[:] = phase
 
     def set_mode(self, mode):
+        if mode == rc.MODE_FM and not self.fm_set:
+            return rc.ARGUMENT_ERROR
         self.mode = mode
-        assert self.a.set_mode(rc.MODE_AM if mode == rc.MODE_FM else mode) == 0
-        assert self.b.set_mode(rc.MODE_AM if mode == rc.MODE_AM else rc.MODE_USB) == 0
+        self._inner_modes()
+        return 0
 
     def process(self, audio):
         audio = np.ascontiguousarray(audio, f32)
