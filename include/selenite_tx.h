@@ -112,5 +112,7 @@ int  selenite_tx_time_process_device(selenite_tx_instance *S, const float *dSrcA
 
 /* the FM transmit mode with its CTCSS tone encoder: selenite_tx_set_fm and what goes with it */
 #include "selenite_tx_fm.h"
+/* the keyed CW path (key states in, shaped carrier at the pitch offset out, sidetone, break-in flag): selenite_tx_set_cw and what goes with it */
+#include "selenite_tx_cw.h"
 
 #endif /* SELENITE_TX_H */

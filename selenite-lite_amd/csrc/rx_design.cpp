@@ -170,3 +170,19 @@ extern "C" uint32_t selenite_tx_tone_step(double hz, double fs_out)
     const double frac = turns - std::floor(turns);          // [0, 1): the step is periodic in whole turns
     return (uint32_t)((uint64_t)std::llround(frac * 4294967296.0) & 0xFFFFFFFFull);
 }
+
+// include/selenite_tx_cw.h: the keying shape for selenite_tx_cw_config::shape_coeffs -- the Hann window w[k] = 0.5 - 0.5 cos(2 pi (k + 1) /
+// (ns + 1)) (no zero end taps), normalised to sum 1 in double and rounded to f32 once.  Its running sum, the step response of the shaping
+// FIR, is a raised-cosine edge of ns samples; ns = 1 is {1.0f}: hard keying.  The window is symmetric, so CMSIS order is its own.
+extern "C" int selenite_tx_design_keyshape(uint32_t ns_taps, float *coeffs)
+{
+    if (ns_taps == 0 || !coeffs) return SELENITE_RX_ARGUMENT_ERROR;
+    const double kPi = 3.14159265358979323846;
+    std::vector<double> w(ns_taps);
+    for (uint32_t k = 0; k < ns_taps / 2 + (ns_taps & 1u); ++k)                     // both halves from one evaluation: symmetric on bits
+        w[k] = w[ns_taps - 1 - k] = 0.5 - 0.5 * std::cos(2.0 * kPi * (double)(k + 1) / ((double)ns_taps + 1.0));
+    double sum = 0.0;
+    for (uint32_t k = 0; k < ns_taps; ++k) sum += w[k];
+    for (uint32_t k = 0; k < ns_taps; ++k) coeffs[k] = (float)(w[k] / sum);
+    return SELENITE_RX_SUCCESS;
+}

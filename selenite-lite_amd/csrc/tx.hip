@@ -39,6 +39,14 @@ struct selenite_tx_instance {
     bool fm_set = false;
     srx::TxFmParams fm{};         // d_tone_step / d_tone_phase live as long as the instance once allocated
     uint32_t *d_tone_step = nullptr, *d_tone_phase = nullptr;
+    // keyed CW (selenite_tx_set_cw, tx_cw.hip); cw.offset holds + offset_step, the mode's sign is applied per call
+    bool cw_set = false;
+    srx::TxCwParams cw{};
+    float *d_shape = nullptr;
+    uint32_t *d_side_step = nullptr, *d_side_phase = nullptr, *d_tx_on = nullptr, *d_hold = nullptr;
+    uint8_t *d_key_state = nullptr;
+    void *d_io_side = nullptr;
+    size_t io_side_bytes = 0;
     hipStream_t stream = nullptr, own_stream = nullptr;
     int status = 0;
     std::string err;
@@ -341,6 +349,12 @@ int reset_state(selenite_tx_instance *S)
     if (p1) TCHK(S, hipMemsetAsync(S->d_int_state, 0, C * 2 * p1 * sizeof(float), S->stream));
     TCHK(S, hipMemsetAsync(S->d_phase, 0, C * sizeof(uint32_t), S->stream));
     if (S->d_tone_phase) TCHK(S, hipMemsetAsync(S->d_tone_phase, 0, C * sizeof(uint32_t), S->stream));
+    if (S->cw_set) {
+        if (S->cw.ns > 1) TCHK(S, hipMemsetAsync(S->d_key_state, 0, C * (S->cw.ns - 1), S->stream));
+        TCHK(S, hipMemsetAsync(S->d_side_phase, 0, C * sizeof(uint32_t), S->stream));
+        TCHK(S, hipMemsetAsync(S->d_tx_on, 0, C * sizeof(uint32_t), S->stream));
+        TCHK(S, hipMemsetAsync(S->d_hold, 0, C * sizeof(uint32_t), S->stream));
+    }
     std::vector<float> gi(C, g.alc_gain_init);
     TCHK(S, hipMemcpyAsync(S->d_gain, gi.data(), C * sizeof(float), hipMemcpyHostToDevice, S->stream));
     TCHK(S, hipStreamSynchronize(S->stream));
@@ -373,6 +387,51 @@ void process_host(selenite_tx_instance *S, const void *src, void *dst, uint32_t 
     if (hipMemcpyAsync(dst, S->d_io_out, nout, hipMemcpyDeviceToHost, S->stream) != hipSuccess ||
         hipStreamSynchronize(S->stream) != hipSuccess)
         fail(S, SELENITE_RX_DEVICE_ERROR, "D2H copy failed");
+}
+
+// keyed CW: every refusal comes before anything is written
+int key_call_ok(selenite_tx_instance *S, const void *key, const void *dst, uint32_t bs, const char *who)
+{
+    if (!S) return SELENITE_RX_ARGUMENT_ERROR;
+    if (!S->cw_set) return fail(S, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": keyed CW is not configured (selenite_tx_set_cw)");
+    if (S->cfg.mode != SELENITE_MODE_CW && S->cfg.mode != SELENITE_MODE_CWR)
+        return fail(S, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": the mode is neither CW nor CWR");
+    if (!key || !dst) return fail(S, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": NULL buffer");
+    if (!block_size_ok(S, bs, who)) return SELENITE_RX_LENGTH_ERROR;
+    if (tx_cw_lds_bytes(make_params(S, bs), S->cw) > 64 * 1024)
+        return fail(S, SELENITE_RX_LENGTH_ERROR, "filter lengths exceed the LDS budget of the TX kernel");
+    return 0;
+}
+
+int run_key(selenite_tx_instance *S, const uint8_t *key, void *dst, void *side, bool q15, uint32_t bs)
+{
+    TCHK(S, hipSetDevice(S->device));
+    const TxParams p = make_params(S, bs);
+    TxCwParams w = S->cw;
+    if (S->cfg.mode == SELENITE_MODE_CWR) w.offset = 0u - w.offset;
+    // the carrier offset went into the phase accumulator: every channel's phase is its own from here on, as after FM
+    S->phase_uniform = false;
+    TCHK(S, launch_tx_cw(p, w, (int)S->cfg.arith, key, q15, dst, side, S->stream));
+    return 0;
+}
+
+int process_key_host(selenite_tx_instance *S, const uint8_t *key, void *dst, void *side, uint32_t bs, bool q15, const char *who)
+{
+    if (int r = key_call_ok(S, key, dst, bs, who)) return r;
+    const selenite_tx_config &g = S->cfg;
+    const size_t esz = q15 ? sizeof(int16_t) : sizeof(float);
+    const size_t nin = (size_t)g.channels * bs, nout = nin * g.interp * 2 * esz, nside = nin * esz;
+    TCHK(S, hipSetDevice(S->device));
+    if (ensure(S, &S->d_io_in, &S->io_in_bytes, nin) || ensure(S, &S->d_io_out, &S->io_out_bytes, nout) ||
+        (side && ensure(S, &S->d_io_side, &S->io_side_bytes, nside)))
+        return S->status;
+    TCHK(S, hipMemcpyAsync(S->d_io_in, key, nin, hipMemcpyHostToDevice, S->stream));
+    if (side && S->cw.side_mix) TCHK(S, hipMemcpyAsync(S->d_io_side, side, nside, hipMemcpyHostToDevice, S->stream));
+    if (int r = run_key(S, static_cast<const uint8_t *>(S->d_io_in), S->d_io_out, side ? S->d_io_side : nullptr, q15, bs)) return r;
+    TCHK(S, hipMemcpyAsync(dst, S->d_io_out, nout, hipMemcpyDeviceToHost, S->stream));
+    if (side) TCHK(S, hipMemcpyAsync(side, S->d_io_side, nside, hipMemcpyDeviceToHost, S->stream));
+    TCHK(S, hipStreamSynchronize(S->stream));
+    return 0;
 }
 
 }  // namespace
@@ -461,7 +520,8 @@ extern "C" void selenite_tx_free(selenite_tx_instance *S)
 {
     if (!S) return;
     void *ptrs[] = { S->d_ic, S->d_hc, S->d_dc, S->d_sintab, S->d_step, S->d_phase, S->d_fir_state, S->d_int_state,
-                     S->d_gain, S->d_io_in, S->d_io_out, S->d_lo, S->d_ttab16, S->d_tone_step, S->d_tone_phase };
+                     S->d_gain, S->d_io_in, S->d_io_out, S->d_lo, S->d_ttab16, S->d_tone_step, S->d_tone_phase,
+                     S->d_shape, S->d_side_step, S->d_side_phase, S->d_tx_on, S->d_hold, S->d_key_state, S->d_io_side };
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (S->own_stream) (void)hipStreamDestroy(S->own_stream);
@@ -616,6 +676,138 @@ extern "C" int selenite_tx_time_process_device(selenite_tx_instance *S, const fl
     TCHK(S, hipEventRecord(ev.e0, S->stream));
     for (uint32_t i = 0; i < iters; ++i)
         if (run(S, src, dst, false, bs)) return S->status;
+    TCHK(S, hipEventRecord(ev.e1, S->stream));
+    TCHK(S, hipEventSynchronize(ev.e1));
+    float ms = 0.0f;
+    TCHK(S, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *ms_per_call = ms / (float)iters;
+    return 0;
+}
+
+// ---- keyed CW (include/selenite_tx_cw.h) ----
+
+extern "C" int selenite_tx_set_cw(selenite_tx_instance *S, const selenite_tx_cw_config *f)
+{
+    if (!S) return SELENITE_RX_ARGUMENT_ERROR;
+    static_assert(sizeof(selenite_tx_cw_config) == 56 && offsetof(selenite_tx_cw_config, side_step) == 32, "selenite_tx_cw_config layout (LP64)");
+    if (!f) {                                               // keyed CW off again, in any mode: the audio entries never needed it
+        S->cw_set = false;
+        return SELENITE_RX_SUCCESS;
+    }
+    if (f->struct_size != sizeof(selenite_tx_cw_config) || f->reserved != 0 || f->side_mix > 1u || f->ns_taps == 0 || !f->shape_coeffs ||
+        !std::isfinite(f->amplitude) || !std::isfinite(f->side_level))
+        return SELENITE_RX_ARGUMENT_ERROR;                  // the previous setting stays
+    float sum = 0.0f;                                       // e[n] of a window that is all key-down: the taps in the FIR's own order
+    for (uint32_t k = 0; k < f->ns_taps; ++k) {
+        if (!std::isfinite(f->shape_coeffs[k])) return SELENITE_RX_ARGUMENT_ERROR;
+        sum = sum + f->shape_coeffs[k];
+    }
+    const size_t C = S->cfg.channels, ns1 = f->ns_taps - 1;
+    const bool first = !S->cw_set, new_len = first || f->ns_taps != S->cw.ns;
+    TCHK(S, hipSetDevice(S->device));
+    TCHK(S, hipStreamSynchronize(S->stream));
+    if (!S->d_side_step) TCHK(S, hipMalloc((void **)&S->d_side_step, C * sizeof(uint32_t)));
+    if (!S->d_side_phase) TCHK(S, hipMalloc((void **)&S->d_side_phase, C * sizeof(uint32_t)));
+    if (!S->d_tx_on) TCHK(S, hipMalloc((void **)&S->d_tx_on, C * sizeof(uint32_t)));
+    if (!S->d_hold) TCHK(S, hipMalloc((void **)&S->d_hold, C * sizeof(uint32_t)));
+    // what depends on ns_taps is allocated before anything of the previous setting is given up
+    float *shape = S->d_shape;
+    uint8_t *ks = S->d_key_state;
+    if (new_len || !shape) {
+        TCHK(S, hipMalloc((void **)&shape, f->ns_taps * sizeof(float)));
+        ks = nullptr;
+        if (ns1 && hipMalloc((void **)&ks, C * ns1) != hipSuccess) {
+            (void)hipFree(shape);
+            return fail(S, SELENITE_RX_DEVICE_ERROR, "hipMalloc(key_state)");
+        }
+    }
+    if (shape != S->d_shape) {
+        if (S->d_shape) (void)hipFree(S->d_shape);
+        if (S->d_key_state) (void)hipFree(S->d_key_state);
+        S->d_shape = shape; S->d_key_state = ks;
+    }
+    std::vector<uint32_t> ss(C);
+    for (size_t c = 0; c < C; ++c) ss[c] = f->side_step ? f->side_step[c] : f->side_step_all;
+    TCHK(S, hipMemcpy(S->d_shape, f->shape_coeffs, f->ns_taps * sizeof(float), hipMemcpyHostToDevice));
+    TCHK(S, hipMemcpy(S->d_side_step, ss.data(), C * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (new_len && ns1) TCHK(S, hipMemset(S->d_key_state, 0, C * ns1));
+    if (first) {                                            // a retune keeps the sidetone's phase and the break-in state
+        TCHK(S, hipMemset(S->d_side_phase, 0, C * sizeof(uint32_t)));
+        TCHK(S, hipMemset(S->d_tx_on, 0, C * sizeof(uint32_t)));
+        TCHK(S, hipMemset(S->d_hold, 0, C * sizeof(uint32_t)));
+    }
+    S->cw = srx::TxCwParams{ f->ns_taps, S->d_shape, sum, f->amplitude, f->side_level, f->offset_step, f->side_mix, f->hang_blocks,
+                             S->d_side_step, S->d_side_phase, S->d_tx_on, S->d_hold, S->d_key_state };
+    S->cw_set = true;
+    return SELENITE_RX_SUCCESS;
+}
+
+extern "C" int selenite_tx_get_cw_state(selenite_tx_instance *S, const selenite_tx_cw_state_view *v)
+{
+    if (!S || !v || !S->cw_set) return SELENITE_RX_ARGUMENT_ERROR;
+    const size_t C = S->cfg.channels, ns1 = S->cw.ns - 1;
+    TCHK(S, hipStreamSynchronize(S->stream));
+    if (v->key_state && ns1) TCHK(S, hipMemcpy(v->key_state, S->d_key_state, C * ns1, hipMemcpyDeviceToHost));
+    if (v->side_phase) TCHK(S, hipMemcpy(v->side_phase, S->d_side_phase, C * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (v->tx_on) TCHK(S, hipMemcpy(v->tx_on, S->d_tx_on, C * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (v->hold) TCHK(S, hipMemcpy(v->hold, S->d_hold, C * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int selenite_tx_set_cw_state(selenite_tx_instance *S, const selenite_tx_cw_state_view *v)
+{
+    if (!S || !v || !S->cw_set) return SELENITE_RX_ARGUMENT_ERROR;
+    const size_t C = S->cfg.channels, ns1 = S->cw.ns - 1;
+    TCHK(S, hipStreamSynchronize(S->stream));
+    if (v->key_state && ns1) {
+        std::vector<uint8_t> ks(C * ns1);
+        for (size_t i = 0; i < ks.size(); ++i) ks[i] = v->key_state[i] ? 1 : 0;
+        TCHK(S, hipMemcpy(S->d_key_state, ks.data(), C * ns1, hipMemcpyHostToDevice));
+    }
+    if (v->side_phase) TCHK(S, hipMemcpy(S->d_side_phase, v->side_phase, C * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (v->tx_on) TCHK(S, hipMemcpy(S->d_tx_on, v->tx_on, C * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (v->hold) TCHK(S, hipMemcpy(S->d_hold, v->hold, C * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" int selenite_tx_process_key_f32_device(selenite_tx_instance *S, const uint8_t *key, float *dst, float *side, uint32_t bs)
+{
+    if (int r = key_call_ok(S, key, dst, bs, "selenite_tx_process_key_f32_device")) return r;
+    return run_key(S, key, dst, side, false, bs);
+}
+extern "C" int selenite_tx_process_key_q15_device(selenite_tx_instance *S, const uint8_t *key, int16_t *dst, int16_t *side, uint32_t bs)
+{
+    if (int r = key_call_ok(S, key, dst, bs, "selenite_tx_process_key_q15_device")) return r;
+    return run_key(S, key, dst, side, true, bs);
+}
+extern "C" int selenite_tx_process_key_f32(selenite_tx_instance *S, const uint8_t *key, float *dst, float *side, uint32_t bs)
+{
+    return process_key_host(S, key, dst, side, bs, false, "selenite_tx_process_key_f32");
+}
+extern "C" int selenite_tx_process_key_q15(selenite_tx_instance *S, const uint8_t *key, int16_t *dst, int16_t *side, uint32_t bs)
+{
+    return process_key_host(S, key, dst, side, bs, true, "selenite_tx_process_key_q15");
+}
+
+extern "C" const uint32_t *selenite_tx_cw_txon_device(selenite_tx_instance *S)
+{
+    return (S && S->cw_set) ? S->d_tx_on : nullptr;
+}
+
+extern "C" int selenite_tx_time_process_key_device(selenite_tx_instance *S, const uint8_t *key, float *dst, float *side, uint32_t bs,
+                                                   uint32_t iters, float *ms_per_call)
+{
+    if (!S || !ms_per_call || iters == 0) return SELENITE_RX_ARGUMENT_ERROR;
+    if (int r = key_call_ok(S, key, dst, bs, "selenite_tx_time_process_key_device")) return r;
+    struct EventPair {                                      // destroyed on every exit path
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
+    TCHK(S, hipEventCreate(&ev.e0));
+    TCHK(S, hipEventCreate(&ev.e1));
+    TCHK(S, hipEventRecord(ev.e0, S->stream));
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int r = run_key(S, key, dst, side, false, bs)) return r;
     TCHK(S, hipEventRecord(ev.e1, S->stream));
     TCHK(S, hipEventSynchronize(ev.e1));
     float ms = 0.0f;

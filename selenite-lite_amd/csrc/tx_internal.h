@@ -45,4 +45,21 @@ struct TxFmParams {
 size_t tx_fm_lds_bytes(const TxParams &p);
 hipError_t launch_tx_fm(const TxParams &p, const TxFmParams &f, int arith, const void *src, bool q15, void *dst, hipStream_t st);
 
+// tx_cw.hip: the keyed CW path (selenite_tx_set_cw, include/selenite_tx_cw.h).  k_tx_cw<ARITH, TOut, SIDE>: key bytes in, I/Q out, one
+// single-wave workgroup per channel; of TxParams it reads the shape (channels, block, L, ni, P, block_size), nco, q15_round, ic, sintab,
+// step, phase and int_state; p.phase is read and written whatever p.nco says
+struct TxCwParams {
+    uint32_t ns;                   // shape taps
+    const float *shape;            // [ns] on the device
+    float shape_sum;               // the taps summed in order from +0.0f: e[n] of a window that is all key-down
+    float amplitude, side_level;
+    uint32_t offset;               // + offset_step (CW) or - offset_step (CWR), modulo 2^32
+    uint32_t side_mix, hang_blocks;
+    const uint32_t *side_step;     // [C]
+    uint32_t *side_phase, *tx_on, *hold;   // [C]
+    uint8_t *key_state;            // [C][ns-1]
+};
+size_t tx_cw_lds_bytes(const TxParams &p, const TxCwParams &w);
+hipError_t launch_tx_cw(const TxParams &p, const TxCwParams &w, int arith, const uint8_t *key, bool q15, void *dst, void *side, hipStream_t st);
+
 }  // namespace srx

@@ -218,6 +218,25 @@ TX_ABI_SYMBOLS = [
 # every symbol include/selenite_tx_fm.h declares (the FM transmit mode; selenite_tx.h includes it)
 TXFM_ABI_SYMBOLS = ["selenite_tx_set_fm", "selenite_tx_get_fm_state", "selenite_tx_set_fm_state", "selenite_tx_tone_step"]
 
+class TxCwConfig(C.Structure):
+    """struct selenite_tx_cw_config (include/selenite_tx_cw.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("ns_taps", C.c_uint32), ("shape_coeffs", f32p), ("amplitude", C.c_float),
+                ("offset_step", C.c_uint32), ("side_level", C.c_float), ("side_step_all", C.c_uint32), ("side_step", u32p),
+                ("side_mix", C.c_uint32), ("hang_blocks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class TxCwStateView(C.Structure):
+    """struct selenite_tx_cw_state_view."""
+    _fields_ = [("key_state", C.POINTER(C.c_uint8)), ("side_phase", u32p), ("tx_on", u32p), ("hold", u32p)]
+
+
+# every symbol include/selenite_tx_cw.h declares (the keyed CW path; selenite_tx.h includes it)
+TXCW_ABI_SYMBOLS = [
+    "selenite_tx_set_cw", "selenite_tx_get_cw_state", "selenite_tx_set_cw_state",
+    "selenite_tx_process_key_f32_device", "selenite_tx_process_key_q15_device", "selenite_tx_process_key_f32", "selenite_tx_process_key_q15",
+    "selenite_tx_cw_txon_device", "selenite_tx_time_process_key_device", "selenite_tx_design_keyshape",
+]
+
 # every symbol include/selenite_ring.h declares
 RING_ABI_SYMBOLS = [
     "selenite_ring_init", "selenite_ring_free", "selenite_ring_status", "selenite_ring_error_string",
@@ -405,6 +424,16 @@ def lib():
             L.selenite_tx_set_fm_state.argtypes = [vp, C.POINTER(TxFmStateView)]
             L.selenite_tx_tone_step.argtypes = [C.c_double, C.c_double]
             L.selenite_tx_tone_step.restype = C.c_uint32
+        if hasattr(L, "selenite_tx_set_cw"):                # (an older build named by SELENITE_RX_LIB lacks the keyed CW path)
+            L.selenite_tx_set_cw.argtypes = [vp, C.POINTER(TxCwConfig)]
+            L.selenite_tx_get_cw_state.argtypes = [vp, C.POINTER(TxCwStateView)]
+            L.selenite_tx_set_cw_state.argtypes = [vp, C.POINTER(TxCwStateView)]
+            for n in ("f32_device", "q15_device", "f32", "q15"):
+                getattr(L, "selenite_tx_process_key_" + n).argtypes = [vp, vp, vp, vp, C.c_uint32]
+            L.selenite_tx_cw_txon_device.argtypes = [vp]
+            L.selenite_tx_cw_txon_device.restype = vp
+            L.selenite_tx_time_process_key_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+            L.selenite_tx_design_keyshape.argtypes = [C.c_uint32, f32p]
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -510,6 +539,15 @@ def ctcss_hz():
 def tone_step(hz, fs_out):
     """phase increment per output sample of a tone (Tx.set_fm tone_step, nco_step): round(hz / fs_out * 2^32)"""
     return int(lib().selenite_tx_tone_step(hz, fs_out))
+
+
+def keyshape(ns):
+    """the keying shape for Tx.set_cw: a Hann window of `ns` taps normalised to sum 1 (selenite_tx_design_keyshape); ns = 1: hard keying"""
+    h = np.empty(int(ns), np.float32)
+    rc = lib().selenite_tx_design_keyshape(int(ns), _fp(h))
+    if rc:
+        raise ValueError("selenite_tx_design_keyshape: %d" % rc)
+    return h
 
 
 def design_interp(ni_taps, interp, cutoff):
@@ -1558,6 +1596,93 @@ class Tx:
         rc = self.L.selenite_tx_set_fm_state(self.h, C.byref(v))
         if rc:
             raise RxError(rc, "selenite_tx_set_fm_state: FM is not configured (set_fm)")
+
+    def set_cw(self, shape, amplitude=1.0, offset_step=0, side_level=0.0, side_step=0, side_mix=0, hang_blocks=0):
+        """the keyed CW path (selenite_tx_set_cw; valid while the mode is MODE_CW or MODE_CWR).  shape: the keying taps (sr.keyshape);
+        offset_step: the pitch as a phase increment per OUTPUT sample; side_step: per AUDIO sample, one value or [channels].
+        Returns the status code."""
+        g = TxCwConfig()
+        taps = np.ascontiguousarray(shape, np.float32).reshape(-1)
+        g.struct_size, g.ns_taps, g.shape_coeffs = C.sizeof(TxCwConfig), taps.size, taps.ctypes.data_as(f32p)
+        g.amplitude, g.offset_step, g.side_level, g.side_mix, g.hang_blocks, g.reserved = amplitude, int(offset_step), side_level, int(side_mix), int(hang_blocks), 0
+        steps = None
+        if np.ndim(side_step):
+            steps = np.ascontiguousarray(side_step, np.uint32)
+            if steps.shape != (self.cfg.channels,):
+                raise ValueError("side_step: one value or [channels]")
+            g.side_step = steps.ctypes.data_as(u32p)
+        else:
+            g.side_step_all = int(side_step)
+        rc = self.L.selenite_tx_set_cw(self.h, C.byref(g))
+        if rc == 0:
+            self._cw_ns = taps.size
+        return rc
+
+    def clear_cw(self):
+        """selenite_tx_set_cw(S, NULL): keyed CW off again"""
+        return self.L.selenite_tx_set_cw(self.h, None)
+
+    def process_key(self, d_key, d_iq, d_side, block_size, q15=False):
+        """key states [channels][block_size] uint8 -> I/Q [channels][block_size * interp][2] and, unless d_side is None, the sidetone
+        [channels][block_size]; device pointers (f32, or int16 with q15=True), asynchronous.  Returns the status code."""
+        f = self.L.selenite_tx_process_key_q15_device if q15 else self.L.selenite_tx_process_key_f32_device
+        return f(self.h, d_key, d_iq, d_side, block_size)
+
+    def process_key_host(self, key, side=None, q15=False):
+        """the host entries: key [channels][n] uint8 -> (status, I/Q, sidetone or None); `side` is the buffer the sidetone is written or
+        mixed into (a copy is returned)"""
+        key = np.ascontiguousarray(key, np.uint8)
+        c, bs = key.shape
+        dt = np.int16 if q15 else np.float32
+        out = np.zeros((c, bs * self.cfg.interp, 2), dt)
+        sd = None if side is None else np.array(side, dt, order="C")
+        f = self.L.selenite_tx_process_key_q15 if q15 else self.L.selenite_tx_process_key_f32
+        rc = f(self.h, key.ctypes.data, out.ctypes.data, None if sd is None else sd.ctypes.data, bs)
+        return rc, out, sd
+
+    def _cw_arrays(self):
+        c = self.cfg.channels
+        return {"key_state": np.zeros((c, getattr(self, "_cw_ns", 1) - 1), np.uint8), "side_phase": np.zeros(c, np.uint32),
+                "tx_on": np.zeros(c, np.uint32), "hold": np.zeros(c, np.uint32)}
+
+    @staticmethod
+    def _cw_view(a):
+        v = TxCwStateView()
+        v.key_state = a["key_state"].ctypes.data_as(C.POINTER(C.c_uint8)) if "key_state" in a and a["key_state"].size else None
+        for k in ("side_phase", "tx_on", "hold"):
+            setattr(v, k, a[k].ctypes.data_as(u32p) if k in a else None)
+        return v
+
+    def cw_state(self):
+        a = self._cw_arrays()
+        v = self._cw_view(a)
+        rc = self.L.selenite_tx_get_cw_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_tx_get_cw_state: keyed CW is not configured (set_cw)")
+        return a
+
+    def set_cw_state(self, a):
+        """members that are missing from `a` are left as they are"""
+        want = self._cw_arrays()
+        a = {k: np.ascontiguousarray(a[k], want[k].dtype) for k in want if k in a}
+        for k, x in a.items():
+            if x.shape != want[k].shape:
+                raise ValueError("%s: %s expected" % (k, want[k].shape))
+        v = self._cw_view(a)
+        rc = self.L.selenite_tx_set_cw_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_tx_set_cw_state: keyed CW is not configured (set_cw)")
+
+    def cw_txon(self):
+        """device pointer of the break-in flags, uint32 [channels] (None before set_cw)"""
+        return self.L.selenite_tx_cw_txon_device(self.h)
+
+    def time_process_key(self, d_key, d_iq, d_side, block_size, iters):
+        ms = C.c_float()
+        rc = self.L.selenite_tx_time_process_key_device(self.h, d_key, d_iq, d_side, block_size, iters, C.byref(ms))
+        if rc:
+            raise RxError(rc, self.L.selenite_tx_error_string(self.h).decode())
+        return ms.value
 
     def time_process(self, d_src, d_dst, block_size, iters):
         ms = C.c_float()
