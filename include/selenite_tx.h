@@ -114,5 +114,7 @@ int  selenite_tx_time_process_device(selenite_tx_instance *S, const float *dSrcA
 #include "selenite_tx_fm.h"
 /* the keyed CW path (key states in, shaped carrier at the pitch offset out, sidetone, break-in flag): selenite_tx_set_cw and what goes with it */
 #include "selenite_tx_cw.h"
+/* the audio input stage (slot-rate L/R frames in: pick, mic gain, decimator, VOX; then the chain): selenite_tx_set_in and what goes with it */
+#include "selenite_tx_in.h"
 
 #endif /* SELENITE_TX_H */

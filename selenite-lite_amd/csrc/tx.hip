@@ -47,6 +47,15 @@ struct selenite_tx_instance {
     uint8_t *d_key_state = nullptr;
     void *d_io_side = nullptr;
     size_t io_side_bytes = 0;
+    // the audio input stage (selenite_tx_set_in, tx_in.hip); in.coeffs, in.dec_state and the VOX rows are the d_in_* below
+    bool in_set = false;
+    srx::TxInParams in{};
+    float in_level_init = 0.0f;
+    float *d_in_coeffs = nullptr, *d_in_dec = nullptr, *d_in_level = nullptr;
+    uint32_t *d_in_open = nullptr, *d_in_hold = nullptr;
+    uint64_t *d_in_opens = nullptr, *d_in_open_blocks = nullptr;
+    void *d_in_audio = nullptr;   // the stage's output of the last frame call: what run() then reads
+    size_t in_audio_bytes = 0;
     hipStream_t stream = nullptr, own_stream = nullptr;
     int status = 0;
     std::string err;
@@ -341,6 +350,20 @@ int upload(selenite_tx_instance *S, T **dp, const T *h, size_t n)
     return 0;
 }
 
+// the input stage's state as the first selenite_tx_set_in leaves it: the decimator tail +0.0f and, with `vox`, level_init, closed, counters 0
+int in_clear_state(selenite_tx_instance *S, bool vox, const std::vector<float> &level_init)
+{
+    const size_t C = S->cfg.channels, h1 = S->in.nt ? S->in.nt - 1 : 0;
+    if (h1) TCHK(S, hipMemsetAsync(S->d_in_dec, 0, C * h1 * sizeof(float), S->stream));
+    if (!vox) return 0;
+    TCHK(S, hipMemcpyAsync(S->d_in_level, level_init.data(), C * sizeof(float), hipMemcpyHostToDevice, S->stream));
+    TCHK(S, hipMemsetAsync(S->d_in_open, 0, C * sizeof(uint32_t), S->stream));
+    TCHK(S, hipMemsetAsync(S->d_in_hold, 0, C * sizeof(uint32_t), S->stream));
+    TCHK(S, hipMemsetAsync(S->d_in_opens, 0, C * sizeof(uint64_t), S->stream));
+    TCHK(S, hipMemsetAsync(S->d_in_open_blocks, 0, C * sizeof(uint64_t), S->stream));
+    return 0;
+}
+
 int reset_state(selenite_tx_instance *S)
 {
     const selenite_tx_config &g = S->cfg;
@@ -355,7 +378,8 @@ int reset_state(selenite_tx_instance *S)
         TCHK(S, hipMemsetAsync(S->d_tx_on, 0, C * sizeof(uint32_t), S->stream));
         TCHK(S, hipMemsetAsync(S->d_hold, 0, C * sizeof(uint32_t), S->stream));
     }
-    std::vector<float> gi(C, g.alc_gain_init);
+    std::vector<float> gi(C, g.alc_gain_init), li(C, S->in_level_init);   // (alive until the stream is drained)
+    if (S->in_set && in_clear_state(S, true, li)) return S->status;
     TCHK(S, hipMemcpyAsync(S->d_gain, gi.data(), C * sizeof(float), hipMemcpyHostToDevice, S->stream));
     TCHK(S, hipStreamSynchronize(S->stream));
     S->phase_host = 0;
@@ -521,7 +545,8 @@ extern "C" void selenite_tx_free(selenite_tx_instance *S)
     if (!S) return;
     void *ptrs[] = { S->d_ic, S->d_hc, S->d_dc, S->d_sintab, S->d_step, S->d_phase, S->d_fir_state, S->d_int_state,
                      S->d_gain, S->d_io_in, S->d_io_out, S->d_lo, S->d_ttab16, S->d_tone_step, S->d_tone_phase,
-                     S->d_shape, S->d_side_step, S->d_side_phase, S->d_tx_on, S->d_hold, S->d_key_state, S->d_io_side };
+                     S->d_shape, S->d_side_step, S->d_side_phase, S->d_tx_on, S->d_hold, S->d_key_state, S->d_io_side,
+                     S->d_in_coeffs, S->d_in_dec, S->d_in_level, S->d_in_open, S->d_in_hold, S->d_in_opens, S->d_in_open_blocks, S->d_in_audio };
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (S->own_stream) (void)hipStreamDestroy(S->own_stream);
@@ -813,5 +838,205 @@ extern "C" int selenite_tx_time_process_key_device(selenite_tx_instance *S, cons
     float ms = 0.0f;
     TCHK(S, hipEventElapsedTime(&ms, ev.e0, ev.e1));
     *ms_per_call = ms / (float)iters;
+    return 0;
+}
+
+// ---- the audio input stage (include/selenite_tx_in.h) ----
+
+namespace {
+
+TxInParams in_params(const selenite_tx_instance *S, uint32_t bs)
+{
+    TxInParams q = S->in;
+    q.channels = S->cfg.channels; q.block = S->cfg.block; q.block_size = bs; q.q15_round = S->cfg.q15_rounding ? 1u : 0u;
+    return q;
+}
+
+// what run() would refuse behind the stage: asked first, so that a refused call moves no state
+bool chain_budget_ok(const selenite_tx_instance *S, uint32_t bs)
+{
+    const TxParams p = make_params(S, bs);
+    if (S->cfg.mode == SELENITE_MODE_FM) return tx_fm_lds_bytes(p) <= 64 * 1024;
+    if (!S->force_generic && tx_fused_ok(S->cfg, S->delay_is_impulse, S->hilb_odd_only, bs)) return true;
+    return tx_lds_bytes(p) <= 64 * 1024;
+}
+
+// frame calls: every refusal comes before anything is written
+int frames_call_ok(selenite_tx_instance *S, const void *frames, const void *dst, uint32_t bs, const char *who)
+{
+    if (!S) return SELENITE_RX_ARGUMENT_ERROR;
+    if (!S->in_set) return fail(S, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": the input stage is not configured (selenite_tx_set_in)");
+    if (!frames || !dst) return fail(S, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": NULL buffer");
+    if (!block_size_ok(S, bs, who)) return SELENITE_RX_LENGTH_ERROR;
+    if (tx_in_lds_bytes(in_params(S, bs)) > 64 * 1024 || !chain_budget_ok(S, bs))
+        return fail(S, SELENITE_RX_LENGTH_ERROR, std::string(who) + ": the layout exceeds the LDS budget of a TX kernel");
+    return 0;
+}
+
+int run_in_stage(selenite_tx_instance *S, const void *frames, bool in_q15, bool out_q15, uint32_t bs)
+{
+    TCHK(S, hipSetDevice(S->device));
+    const size_t need = (size_t)S->cfg.channels * bs * (out_q15 ? sizeof(int16_t) : sizeof(float));
+    if (ensure(S, &S->d_in_audio, &S->in_audio_bytes, need)) return S->status;
+    TCHK(S, launch_tx_in(in_params(S, bs), frames, in_q15, S->d_in_audio, out_q15, S->stream));
+    return 0;
+}
+
+int run_frames(selenite_tx_instance *S, const void *frames, bool in_q15, void *dst, bool out_q15, uint32_t bs)
+{
+    if (int r = run_in_stage(S, frames, in_q15, out_q15, bs)) return r;
+    return run(S, S->d_in_audio, dst, out_q15, bs);              // the existing chain on the stage's audio, unchanged
+}
+
+int process_frames_host(selenite_tx_instance *S, const void *frames, void *dst, uint32_t bs, bool q15, const char *who)
+{
+    if (int r = frames_call_ok(S, frames, dst, bs, who)) return r;
+    const selenite_tx_config &g = S->cfg;
+    const size_t esz = q15 ? sizeof(int16_t) : sizeof(float);
+    const size_t fw = S->in.pick == SELENITE_TX_IN_MONO ? 1 : 2;
+    const size_t nin = (size_t)g.channels * bs * S->in.M * fw * esz, nout = (size_t)g.channels * bs * g.interp * 2 * esz;
+    TCHK(S, hipSetDevice(S->device));
+    if (ensure(S, &S->d_io_in, &S->io_in_bytes, nin) || ensure(S, &S->d_io_out, &S->io_out_bytes, nout)) return S->status;
+    TCHK(S, hipMemcpyAsync(S->d_io_in, frames, nin, hipMemcpyHostToDevice, S->stream));
+    if (int r = run_frames(S, S->d_io_in, q15, S->d_io_out, q15, bs)) return r;
+    TCHK(S, hipMemcpyAsync(dst, S->d_io_out, nout, hipMemcpyDeviceToHost, S->stream));
+    TCHK(S, hipStreamSynchronize(S->stream));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int selenite_tx_set_in(selenite_tx_instance *S, const selenite_tx_in_config *f)
+{
+    if (!S) return SELENITE_RX_ARGUMENT_ERROR;
+    static_assert(sizeof(selenite_tx_in_config) == 72 && offsetof(selenite_tx_in_config, coeffs) == 16 && offsetof(selenite_tx_in_config, meter) == 32 &&
+                  sizeof(selenite_tx_in_state_view) == 48, "selenite_tx_in_config layout (LP64)");
+    if (!f) {                                               // the stage off again, in any mode: the audio and key entries never needed it
+        S->in_set = false;
+        return SELENITE_RX_SUCCESS;
+    }
+    if (f->struct_size != sizeof(selenite_tx_in_config) || f->reserved != 0 || !(f->M == 1 || f->M == 2 || f->M == 4 || f->M == 8) ||
+        f->nd_taps > 256 || (f->nd_taps == 0 && f->M != 1) || (f->nd_taps && !f->coeffs) || f->pick > SELENITE_TX_IN_MIX ||
+        !std::isfinite(f->gain) || f->vox > 1u)
+        return SELENITE_RX_ARGUMENT_ERROR;                  // the previous setting stays
+    for (uint32_t k = 0; k < f->nd_taps; ++k)
+        if (!std::isfinite(f->coeffs[k])) return SELENITE_RX_ARGUMENT_ERROR;
+    const selenite_rx_meter_config &m = f->meter;
+    if (f->vox) {                                           // selenite_rx_set_meter's own rules, sense ABOVE
+        if (m.struct_size != sizeof(selenite_rx_meter_config) || m.sense != SELENITE_RX_SQ_ABOVE || m.gate > 1u || m.hang > 65535u ||
+            !(m.attack > 0.0f && m.attack <= 1.0f) || !(m.decay > 0.0f && m.decay <= 1.0f) ||
+            !(std::isfinite(m.open_level) && m.open_level >= 0.0f) || !(std::isfinite(m.close_level) && m.close_level >= 0.0f) ||
+            !(m.close_level <= m.open_level) || !(std::isfinite(m.level_init) && m.level_init >= 0.0f))
+            return SELENITE_RX_ARGUMENT_ERROR;
+    }
+    const size_t C = S->cfg.channels, h1 = f->nd_taps ? f->nd_taps - 1 : 0;
+    const bool first = !S->in_set, new_len = first || f->nd_taps != S->in.nt;
+    TCHK(S, hipSetDevice(S->device));
+    TCHK(S, hipStreamSynchronize(S->stream));
+    if (!S->d_in_level) TCHK(S, hipMalloc((void **)&S->d_in_level, C * sizeof(float)));
+    if (!S->d_in_open) TCHK(S, hipMalloc((void **)&S->d_in_open, C * sizeof(uint32_t)));
+    if (!S->d_in_hold) TCHK(S, hipMalloc((void **)&S->d_in_hold, C * sizeof(uint32_t)));
+    if (!S->d_in_opens) TCHK(S, hipMalloc((void **)&S->d_in_opens, C * sizeof(uint64_t)));
+    if (!S->d_in_open_blocks) TCHK(S, hipMalloc((void **)&S->d_in_open_blocks, C * sizeof(uint64_t)));
+    // what depends on nd_taps is allocated before anything of the previous setting is given up
+    float *coeffs = S->d_in_coeffs, *dec = S->d_in_dec;
+    if (new_len) {
+        coeffs = dec = nullptr;
+        if (f->nd_taps) TCHK(S, hipMalloc((void **)&coeffs, f->nd_taps * sizeof(float)));
+        if (h1 && hipMalloc((void **)&dec, C * h1 * sizeof(float)) != hipSuccess) {
+            (void)hipFree(coeffs);
+            return fail(S, SELENITE_RX_DEVICE_ERROR, "hipMalloc(dec_state)");
+        }
+        if (S->d_in_coeffs) (void)hipFree(S->d_in_coeffs);
+        if (S->d_in_dec) (void)hipFree(S->d_in_dec);
+        S->d_in_coeffs = coeffs; S->d_in_dec = dec;
+    }
+    if (f->nd_taps) TCHK(S, hipMemcpy(S->d_in_coeffs, f->coeffs, f->nd_taps * sizeof(float), hipMemcpyHostToDevice));
+    TxInParams q{};
+    q.M = f->M; q.nt = f->nd_taps; q.pick = f->pick; q.gain = f->gain; q.vox = f->vox;
+    if (f->vox) {
+        q.gate = m.gate; q.hang = m.hang; q.attack = m.attack; q.decay = m.decay; q.open_level = m.open_level; q.close_level = m.close_level;
+        S->in_level_init = m.level_init;
+    }
+    q.coeffs = S->d_in_coeffs; q.dec_state = S->d_in_dec; q.level = S->d_in_level; q.open = S->d_in_open; q.hold = S->d_in_hold;
+    q.opens = S->d_in_opens; q.open_blocks = S->d_in_open_blocks;
+    S->in = q;
+    if (first || new_len) {                                 // a retune keeps the decimator tail (same nd_taps) and the VOX state
+        if (first && !f->vox) S->in_level_init = 0.0f;
+        const std::vector<float> li(C, S->in_level_init);
+        if (in_clear_state(S, first, li)) return S->status;
+        TCHK(S, hipStreamSynchronize(S->stream));
+    }
+    S->in_set = true;
+    return SELENITE_RX_SUCCESS;
+}
+
+static int in_state_copy(selenite_tx_instance *S, const selenite_tx_in_state_view *v, bool to_host)
+{
+    if (!S || !v || !S->in_set) return SELENITE_RX_ARGUMENT_ERROR;
+    const size_t C = S->cfg.channels, h1 = S->in.nt ? S->in.nt - 1 : 0;
+    TCHK(S, hipStreamSynchronize(S->stream));
+    struct Row { void *dev; void *host; size_t bytes; };
+    const Row rows[] = { { S->d_in_dec, v->dec_state, C * h1 * sizeof(float) }, { S->d_in_level, v->level, C * sizeof(float) },
+                         { S->d_in_open, v->open, C * sizeof(uint32_t) }, { S->d_in_hold, v->hold, C * sizeof(uint32_t) },
+                         { S->d_in_opens, v->opens, C * sizeof(uint64_t) }, { S->d_in_open_blocks, v->open_blocks, C * sizeof(uint64_t) } };
+    for (const Row &r : rows) {
+        if (!r.host || !r.bytes) continue;                  // NULL members are skipped
+        if (to_host) TCHK(S, hipMemcpy(r.host, r.dev, r.bytes, hipMemcpyDeviceToHost));
+        else TCHK(S, hipMemcpy(r.dev, r.host, r.bytes, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+extern "C" int selenite_tx_get_in_state(selenite_tx_instance *S, const selenite_tx_in_state_view *v) { return in_state_copy(S, v, true); }
+extern "C" int selenite_tx_set_in_state(selenite_tx_instance *S, const selenite_tx_in_state_view *v) { return in_state_copy(S, v, false); }
+
+extern "C" int selenite_tx_process_frames_f32_device(selenite_tx_instance *S, const float *frames, float *dst, uint32_t bs)
+{
+    if (int r = frames_call_ok(S, frames, dst, bs, "selenite_tx_process_frames_f32_device")) return r;
+    return run_frames(S, frames, false, dst, false, bs);
+}
+extern "C" int selenite_tx_process_frames_q15_device(selenite_tx_instance *S, const int16_t *frames, int16_t *dst, uint32_t bs)
+{
+    if (int r = frames_call_ok(S, frames, dst, bs, "selenite_tx_process_frames_q15_device")) return r;
+    return run_frames(S, frames, true, dst, true, bs);
+}
+extern "C" int selenite_tx_process_frames_q15_f32_device(selenite_tx_instance *S, const int16_t *frames, float *dst, uint32_t bs)
+{
+    if (int r = frames_call_ok(S, frames, dst, bs, "selenite_tx_process_frames_q15_f32_device")) return r;
+    return run_frames(S, frames, true, dst, false, bs);
+}
+extern "C" int selenite_tx_process_frames_f32(selenite_tx_instance *S, const float *frames, float *dst, uint32_t bs)
+{
+    return process_frames_host(S, frames, dst, bs, false, "selenite_tx_process_frames_f32");
+}
+extern "C" int selenite_tx_process_frames_q15(selenite_tx_instance *S, const int16_t *frames, int16_t *dst, uint32_t bs)
+{
+    return process_frames_host(S, frames, dst, bs, true, "selenite_tx_process_frames_q15");
+}
+
+extern "C" const uint32_t *selenite_tx_in_vox_device(selenite_tx_instance *S) { return (S && S->in_set) ? S->d_in_open : nullptr; }
+extern "C" const void *selenite_tx_in_audio_device(selenite_tx_instance *S) { return (S && S->in_set) ? S->d_in_audio : nullptr; }
+
+extern "C" int selenite_tx_time_in_stage_device(selenite_tx_instance *S, const void *frames, uint32_t kind, uint32_t bs, uint32_t iters,
+                                                float *ms_per_launch)
+{
+    if (!S || !ms_per_launch || iters == 0 || kind > SELENITE_TX_IN_Q15_F32) return SELENITE_RX_ARGUMENT_ERROR;
+    if (int r = frames_call_ok(S, frames, ms_per_launch, bs, "selenite_tx_time_in_stage_device")) return r;
+    const bool in_q15 = kind != SELENITE_TX_IN_F32, out_q15 = kind == SELENITE_TX_IN_Q15;
+    struct EventPair {                                      // destroyed on every exit path
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
+    TCHK(S, hipEventCreate(&ev.e0));
+    TCHK(S, hipEventCreate(&ev.e1));
+    if (int r = run_in_stage(S, frames, in_q15, out_q15, bs)) return r;      // (grows the audio buffer outside the timed span)
+    TCHK(S, hipEventRecord(ev.e0, S->stream));
+    for (uint32_t i = 0; i < iters; ++i)
+        if (int r = run_in_stage(S, frames, in_q15, out_q15, bs)) return r;
+    TCHK(S, hipEventRecord(ev.e1, S->stream));
+    TCHK(S, hipEventSynchronize(ev.e1));
+    float ms = 0.0f;
+    TCHK(S, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *ms_per_launch = ms / (float)iters;
     return 0;
 }

@@ -62,4 +62,21 @@ struct TxCwParams {
 size_t tx_cw_lds_bytes(const TxParams &p, const TxCwParams &w);
 hipError_t launch_tx_cw(const TxParams &p, const TxCwParams &w, int arith, const uint8_t *key, bool q15, void *dst, void *side, hipStream_t st);
 
+// tx_in.hip: the audio input stage (selenite_tx_set_in, include/selenite_tx_in.h).  k_tx_in<M, PICK, TIn, TOut>: slot-rate frames in, the
+// chain's audio out, one single-wave workgroup per channel row; no arith mode (nothing is contracted)
+struct TxInParams {
+    uint32_t channels, block, block_size;          // DSP block and call length in AUDIO samples (the stage's outputs)
+    uint32_t M, nt, pick;
+    uint32_t vox, gate, hang, q15_round;
+    float gain, attack, decay, open_level, close_level;
+    const float *coeffs;                           // [nt] on the device
+    float *dec_state;                              // [C][nt-1]
+    float *level;                                  // [C]
+    uint32_t *open, *hold;                         // [C]
+    uint64_t *opens, *open_blocks;                 // [C]
+};
+uint32_t tx_in_tile(const TxInParams &q);          // outputs of a tile: a whole number of DSP blocks
+size_t tx_in_lds_bytes(const TxInParams &q);       // the sum in 64 bits
+hipError_t launch_tx_in(const TxInParams &q, const void *frames, bool in_q15, void *audio, bool out_q15, hipStream_t st);
+
 }  // namespace srx

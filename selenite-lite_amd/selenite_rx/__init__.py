@@ -25,6 +25,8 @@ NR_OFF, NR_DENOISE, NR_NOTCH = 0, 1, 2                         # selenite_rx_set
 OUT_MONO, OUT_STEREO = 0, 1                                    # selenite_rx_set_out: the output stage's frame format
 WINDOW_HANN, WINDOW_BLACKMAN_HARRIS = 0, 1                     # selenite_rx_design_window
 SQ_ABOVE, SQ_BELOW = 0, 1                                      # selenite_rx_set_meter: the squelch's sense
+IN_MONO, IN_LEFT, IN_RIGHT, IN_MIX = 0, 1, 2, 3                # selenite_tx_set_in: which words of a frame make the audio
+IN_F32, IN_Q15, IN_Q15_F32 = 0, 1, 2                           # the frame entries: f32 -> f32 I/Q, int16 -> int16 I/Q, int16 -> f32 I/Q
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -237,6 +239,25 @@ TXCW_ABI_SYMBOLS = [
     "selenite_tx_cw_txon_device", "selenite_tx_time_process_key_device", "selenite_tx_design_keyshape",
 ]
 
+class TxInConfig(C.Structure):
+    """struct selenite_tx_in_config (include/selenite_tx_in.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("M", C.c_uint32), ("nd_taps", C.c_uint32), ("pick", C.c_uint32), ("coeffs", f32p),
+                ("gain", C.c_float), ("vox", C.c_uint32), ("meter", MeterConfig), ("reserved", C.c_uint32)]
+
+
+class TxInStateView(C.Structure):
+    """struct selenite_tx_in_state_view."""
+    _fields_ = [("dec_state", f32p), ("level", f32p), ("open", u32p), ("hold", u32p), ("opens", u64p), ("open_blocks", u64p)]
+
+
+# every symbol include/selenite_tx_in.h declares (the audio input stage; selenite_tx.h includes it)
+TXIN_ABI_SYMBOLS = [
+    "selenite_tx_set_in", "selenite_tx_get_in_state", "selenite_tx_set_in_state",
+    "selenite_tx_process_frames_f32_device", "selenite_tx_process_frames_q15_device", "selenite_tx_process_frames_q15_f32_device",
+    "selenite_tx_process_frames_f32", "selenite_tx_process_frames_q15",
+    "selenite_tx_in_vox_device", "selenite_tx_in_audio_device", "selenite_tx_time_in_stage_device",
+]
+
 # every symbol include/selenite_ring.h declares
 RING_ABI_SYMBOLS = [
     "selenite_ring_init", "selenite_ring_free", "selenite_ring_status", "selenite_ring_error_string",
@@ -434,6 +455,17 @@ def lib():
             L.selenite_tx_cw_txon_device.restype = vp
             L.selenite_tx_time_process_key_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
             L.selenite_tx_design_keyshape.argtypes = [C.c_uint32, f32p]
+        if hasattr(L, "selenite_tx_set_in"):                # (an older build named by SELENITE_RX_LIB lacks the audio input stage)
+            L.selenite_tx_set_in.argtypes = [vp, C.POINTER(TxInConfig)]
+            L.selenite_tx_get_in_state.argtypes = [vp, C.POINTER(TxInStateView)]
+            L.selenite_tx_set_in_state.argtypes = [vp, C.POINTER(TxInStateView)]
+            for n in ("f32_device", "q15_device", "q15_f32_device", "f32", "q15"):
+                getattr(L, "selenite_tx_process_frames_" + n).argtypes = [vp, vp, vp, C.c_uint32]
+            L.selenite_tx_in_vox_device.argtypes = [vp]
+            L.selenite_tx_in_vox_device.restype = vp
+            L.selenite_tx_in_audio_device.argtypes = [vp]
+            L.selenite_tx_in_audio_device.restype = vp
+            L.selenite_tx_time_in_stage_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -1680,6 +1712,96 @@ class Tx:
     def time_process_key(self, d_key, d_iq, d_side, block_size, iters):
         ms = C.c_float()
         rc = self.L.selenite_tx_time_process_key_device(self.h, d_key, d_iq, d_side, block_size, iters, C.byref(ms))
+        if rc:
+            raise RxError(rc, self.L.selenite_tx_error_string(self.h).decode())
+        return ms.value
+
+    def set_in(self, M=1, coeffs=None, pick=IN_MONO, gain=1.0, vox=None):
+        """the audio input stage (selenite_tx_set_in): slot-rate frames -> pick -> gain -> arm_fir_decimate_f32 by M -> VOX -> the chain.
+        coeffs: the decimator's taps in CMSIS order (None or empty: no FIR, M = 1 only); vox: None (off) or a dict of
+        selenite_rx_meter_config fields (gate, hang, attack, decay, open_level, close_level, level_init; sense defaults to SQ_ABOVE).
+        Returns the status code."""
+        g = TxInConfig()
+        taps = np.zeros(0, np.float32) if coeffs is None else np.ascontiguousarray(coeffs, np.float32).reshape(-1)
+        g.struct_size, g.M, g.nd_taps, g.pick, g.gain, g.reserved = C.sizeof(TxInConfig), int(M), taps.size, int(pick), gain, 0
+        g.coeffs = taps.ctypes.data_as(f32p) if taps.size else None
+        if vox is not None:
+            v = dict(sense=SQ_ABOVE, gate=0, hang=0, attack=0.5, decay=0.125, open_level=1e-6, close_level=5e-7, level_init=0.0)
+            v.update(vox)
+            g.vox = 1
+            g.meter.struct_size = C.sizeof(MeterConfig)
+            for k, x in v.items():
+                setattr(g.meter, k, x)
+        rc = self.L.selenite_tx_set_in(self.h, C.byref(g))
+        if rc == 0:
+            self._in_nt, self._in_M, self._in_fw = taps.size, int(M), 1 if int(pick) == IN_MONO else 2
+        return rc
+
+    def clear_in(self):
+        """selenite_tx_set_in(S, NULL): the input stage off again"""
+        return self.L.selenite_tx_set_in(self.h, None)
+
+    def process_frames(self, d_frames, d_iq, block_size, kind=IN_F32):
+        """frames [channels][block_size * M * (1 or 2)] -> I/Q [channels][block_size * interp][2]; device pointers, asynchronous.
+        kind: IN_F32 (f32 frames, f32 I/Q), IN_Q15 (int16, int16) or IN_Q15_F32 (int16 frames, f32 I/Q).  Returns the status code."""
+        f = (self.L.selenite_tx_process_frames_f32_device, self.L.selenite_tx_process_frames_q15_device,
+             self.L.selenite_tx_process_frames_q15_f32_device)[kind]
+        return f(self.h, d_frames, d_iq, block_size)
+
+    def process_frames_host(self, frames, q15=False):
+        """the host entries: frames [channels][n * M * (1 or 2)] -> (status, I/Q)"""
+        dt = np.int16 if q15 else np.float32
+        frames = np.ascontiguousarray(frames, dt)
+        c = frames.shape[0]
+        bs = frames[0].size // (getattr(self, "_in_M", 1) * getattr(self, "_in_fw", 1))
+        out = np.zeros((c, bs * self.cfg.interp, 2), dt)
+        f = self.L.selenite_tx_process_frames_q15 if q15 else self.L.selenite_tx_process_frames_f32
+        rc = f(self.h, frames.ctypes.data, out.ctypes.data, bs)
+        return rc, out
+
+    def _in_arrays(self):
+        c = self.cfg.channels
+        return {"dec_state": np.zeros((c, max(getattr(self, "_in_nt", 0) - 1, 0)), np.float32), "level": np.zeros(c, np.float32),
+                "open": np.zeros(c, np.uint32), "hold": np.zeros(c, np.uint32), "opens": np.zeros(c, np.uint64),
+                "open_blocks": np.zeros(c, np.uint64)}
+
+    @staticmethod
+    def _in_view(a):
+        v = TxInStateView()
+        for k, t in (("dec_state", f32p), ("level", f32p), ("open", u32p), ("hold", u32p), ("opens", u64p), ("open_blocks", u64p)):
+            setattr(v, k, a[k].ctypes.data_as(t) if k in a and a[k].size else None)
+        return v
+
+    def in_state(self):
+        a = self._in_arrays()
+        rc = self.L.selenite_tx_get_in_state(self.h, C.byref(self._in_view(a)))
+        if rc:
+            raise RxError(rc, "selenite_tx_get_in_state: the input stage is not configured (set_in)")
+        return a
+
+    def set_in_state(self, a):
+        """members that are missing from `a` are left as they are"""
+        want = self._in_arrays()
+        a = {k: np.ascontiguousarray(a[k], want[k].dtype) for k in want if k in a}
+        for k, x in a.items():
+            if x.shape != want[k].shape:
+                raise ValueError("%s: %s expected" % (k, want[k].shape))
+        rc = self.L.selenite_tx_set_in_state(self.h, C.byref(self._in_view(a)))
+        if rc:
+            raise RxError(rc, "selenite_tx_set_in_state: the input stage is not configured (set_in)")
+
+    def in_vox(self):
+        """device pointer of the VOX flags, uint32 [channels] (None before set_in)"""
+        return self.L.selenite_tx_in_vox_device(self.h)
+
+    def in_audio_device(self):
+        """device pointer of the stage's output of the last frame call, [channels][block_size] in the entry's audio type (None before it)"""
+        return self.L.selenite_tx_in_audio_device(self.h)
+
+    def time_in_stage(self, d_frames, block_size, iters, kind=IN_F32):
+        """mean ms of the stage kernel alone over `iters` launches"""
+        ms = C.c_float()
+        rc = self.L.selenite_tx_time_in_stage_device(self.h, d_frames, kind, block_size, iters, C.byref(ms))
         if rc:
             raise RxError(rc, self.L.selenite_tx_error_string(self.h).decode())
         return ms.value
