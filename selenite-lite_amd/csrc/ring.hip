@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/selenite_ring.h"
+#include "hip_event_pair.h"
 #include "../../include/selenite_rx.h"
 
 struct selenite_ring {
@@ -342,10 +343,7 @@ extern "C" int selenite_ring_time_device(selenite_ring *R, const int16_t *dSrc, 
 {
     if (!R || !ms_per_pair || iters == 0) return SELENITE_RX_ARGUMENT_ERROR;
     if (!size_ok(R, size_words, "selenite_ring_time_device")) return R->status;
-    struct EventPair {                                      // destroyed on every exit path
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
+    EventPair ev;                                           // destroyed on every exit path
     hipEvent_t &e0 = ev.e0, &e1 = ev.e1;
     RCHK(R, hipEventCreate(&e0));
     RCHK(R, hipEventCreate(&e1));

@@ -51,30 +51,10 @@ static bool mode_valid(uint8_t m, uint32_t nh_taps)
 
 static void classify_coeffs(selenite_rx_instance *S)
 {
-    const uint32_t nh = S->cfg.nh_taps;
-    S->delay_is_impulse = false;
-    S->hilb_odd_only = false;
-    if (!nh) return;
-    // delay FIR that is exactly a unit impulse: arm_fir_f32 then returns x + 0.0f
-    int ones = 0, idx = -1;
-    bool rest_zero = true;
-    for (uint32_t k = 0; k < nh; ++k) {
-        const float v = S->h_delay[k];
-        if (v == 1.0f) { ++ones; idx = (int)k; }
-        else if (!(v == 0.0f && !std::signbit(v))) rest_zero = false;
-    }
-    if (ones == 1 && rest_zero) { S->delay_is_impulse = true; S->delay_index = idx; }
-    // type-III Hilbert: taps at even distance from the centre are exactly +0.0f
-    if (nh % 2 == 1) {
-        const int c = (int)(nh - 1) / 2;
-        bool ok = true;
-        for (uint32_t k = 0; k < nh && ok; ++k)
-            if ((((int)k - c) & 1) == 0) {
-                const float v = S->h_hilb[k];
-                if (!(v == 0.0f && !std::signbit(v))) ok = false;
-            }
-        S->hilb_odd_only = ok;
-    }
+    const TapClass t = classify_taps(S->h_delay.data(), S->h_hilb.data(), S->cfg.nh_taps);
+    S->delay_is_impulse = t.delay_is_impulse;
+    S->hilb_odd_only = t.hilb_odd_only;
+    if (t.delay_is_impulse) S->delay_index = t.delay_index;
 }
 
 static void free_device(selenite_rx_instance *S)

@@ -10,23 +10,7 @@ static int time_process(selenite_rx_instance *S, const void *src, void *dst, boo
     if (!S || !ms_per_call || iters == 0) return SELENITE_RX_ARGUMENT_ERROR;
     if (!block_size_ok(S, blockSize, who)) return S->status;
     HIPCHK(S, hipSetDevice(S->device));
-    struct EventPair {                                     // destroyed on every exit path
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-    } ev;
-    HIPCHK(S, hipEventCreate(&ev.e0));
-    HIPCHK(S, hipEventCreate(&ev.e1));
-    HIPCHK(S, hipEventRecord(ev.e0, S->stream));
-    for (uint32_t i = 0; i < iters; ++i) {
-        int rc = run_call(S, src, q15, dst, q15, blockSize, kAll, nullptr);
-        if (rc) return rc;
-    }
-    HIPCHK(S, hipEventRecord(ev.e1, S->stream));
-    HIPCHK(S, hipEventSynchronize(ev.e1));
-    float ms = 0.0f;
-    HIPCHK(S, hipEventElapsedTime(&ms, ev.e0, ev.e1));
-    *ms_per_call = ms / (float)iters;
-    return SELENITE_RX_SUCCESS;
+    return timed_loop(S, iters, ms_per_call, [&] { return run_call(S, src, q15, dst, q15, blockSize, kAll, nullptr); });
 }
 
 extern "C" int selenite_rx_time_process_device(selenite_rx_instance *S, const float *dSrcIQ, float *dDstAudio,

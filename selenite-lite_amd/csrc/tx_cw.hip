@@ -9,11 +9,13 @@
 // A DSP block whose key window (history and block) is all up or all down skips the shaping FIR: with every e0 = 1.0f the accumulator
 // takes the taps themselves in order (1.0f * c is c), which is TxCwParams::shape_sum, summed in that order on the host; with every
 // e0 = +0.0f each product is +-0.0f and the accumulator, started at +0.0f, stays +0.0f under round-to-nearest (finite taps).
+// Kernel, launcher and the host side of the path: selenite_tx_set_cw, its state accessors and the key entries.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 
 #include "rx_device.h"
-#include "tx_internal.h"
+#include "tx_host.h"
 
 namespace srx {
 
@@ -284,4 +286,144 @@ hipError_t launch_tx_cw(const TxParams &p, const TxCwParams &w, int arith, const
     return fma ? launch_cw<1, float>(p, w, key, dst, side, st) : launch_cw<0, float>(p, w, key, dst, side, st);
 }
 
+// ---- the host side (tx_host.h) ----
+
+void tx_cw_free(selenite_tx_instance *S)
+{
+    selenite_tx_instance::Cw &W = S->cw;
+    dev_free(W.d_shape, W.d_side_step, W.d_side_phase, W.d_tx_on, W.d_hold, W.d_key_state, W.d_io_side);
+}
+
+int tx_cw_reset(selenite_tx_instance *S)
+{
+    const selenite_tx_instance::Cw &W = S->cw;
+    const size_t C = S->cfg.channels;
+    if (!W.set) return 0;
+    if (W.p.ns > 1) HIPCHK(S, hipMemsetAsync(W.d_key_state, 0, C * (W.p.ns - 1), S->stream));
+    for (uint32_t *row : { W.d_side_phase, W.d_tx_on, W.d_hold }) HIPCHK(S, hipMemsetAsync(row, 0, C * sizeof(uint32_t), S->stream));
+    return 0;
+}
+
+// keyed CW: every refusal comes before anything is written
+static int key_call_ok(selenite_tx_instance *S, const void *key, const void *dst, uint32_t bs, const char *who)
+{
+    if (!S) return SELENITE_RX_ARGUMENT_ERROR;
+    if (!S->cw.set) return fail(S, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": keyed CW is not configured (selenite_tx_set_cw)");
+    if (S->cfg.mode != SELENITE_MODE_CW && S->cfg.mode != SELENITE_MODE_CWR)
+        return fail(S, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": the mode is neither CW nor CWR");
+    if (!key || !dst) return fail(S, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": NULL buffer");
+    if (!block_size_ok(S, bs, who)) return SELENITE_RX_LENGTH_ERROR;
+    if (decide(S, make_params(S, bs), true).refused)
+        return fail(S, SELENITE_RX_LENGTH_ERROR, "filter lengths exceed the LDS budget of the TX kernel");
+    return 0;
+}
+
+static int run_key(selenite_tx_instance *S, const uint8_t *key, void *dst, void *side, bool q15, uint32_t bs)
+{
+    HIPCHK(S, hipSetDevice(S->device));
+    const TxParams p = make_params(S, bs);
+    TxCwParams w = S->cw.p;
+    if (S->cfg.mode == SELENITE_MODE_CWR) w.offset = 0u - w.offset;
+    if (decide(S, p, true).clears_uniform) S->phase_uniform = false;   // the carrier offset went into the phase accumulator, as after FM
+    HIPCHK(S, launch_tx_cw(p, w, (int)S->cfg.arith, key, q15, dst, side, S->stream));
+    return 0;
+}
+
+static int process_key_device(selenite_tx_instance *S, const uint8_t *key, void *dst, void *side, uint32_t bs, bool q15, const char *who)
+{
+    if (int r = key_call_ok(S, key, dst, bs, who)) return r;
+    return run_key(S, key, dst, side, q15, bs);
+}
+
+static int process_key_host(selenite_tx_instance *S, const uint8_t *key, void *dst, void *side, uint32_t bs, bool q15, const char *who)
+{
+    if (int r = key_call_ok(S, key, dst, bs, who)) return r;
+    selenite_tx_instance::Cw &W = S->cw;
+    const size_t nin = (size_t)S->cfg.channels * bs, nside = nin * sample_bytes(q15), nout = nside * S->cfg.interp * 2;
+    return staged_call(S, { { key, nin, kToDevice, &S->d_io_in, &S->io_in_bytes }, { dst, nout, kToHost, &S->d_io_out, &S->io_out_bytes },
+                            { side, nside, W.p.side_mix ? kToDevice | kToHost : kToHost, &W.d_io_side, &W.io_side_bytes } },
+                       [&] { return run_key(S, static_cast<const uint8_t *>(S->d_io_in), S->d_io_out, side ? W.d_io_side : nullptr, q15, bs); });
+}
+
+static int cw_state_copy(selenite_tx_instance *S, const selenite_tx_cw_state_view *v, bool to_host)
+{
+    if (!S || !v || !S->cw.set) return SELENITE_RX_ARGUMENT_ERROR;
+    const selenite_tx_instance::Cw &W = S->cw;
+    const size_t C = S->cfg.channels, nk = C * (W.p.ns - 1);
+    std::vector<uint8_t> ks;                                // into the device: any non-zero byte is key-down
+    if (!to_host && v->key_state) ks.assign(v->key_state, v->key_state + nk);
+    for (uint8_t &k : ks) k = k ? 1 : 0;
+    return copy_rows(S, to_host, { { W.d_key_state, ks.empty() ? v->key_state : ks.data(), nk }, { W.d_side_phase, v->side_phase, C * sizeof(uint32_t) },
+                                   { W.d_tx_on, v->tx_on, C * sizeof(uint32_t) }, { W.d_hold, v->hold, C * sizeof(uint32_t) } });
+}
+
 }  // namespace srx
+
+using namespace srx;
+
+extern "C" int selenite_tx_set_cw(selenite_tx_instance *S, const selenite_tx_cw_config *f)
+{
+    if (!S) return SELENITE_RX_ARGUMENT_ERROR;
+    static_assert(sizeof(selenite_tx_cw_config) == 56 && offsetof(selenite_tx_cw_config, side_step) == 32, "selenite_tx_cw_config layout (LP64)");
+    selenite_tx_instance::Cw &W = S->cw;
+    if (!f) {                                               // keyed CW off again, in any mode: the audio entries never needed it
+        W.set = false;
+        return SELENITE_RX_SUCCESS;
+    }
+    if (f->struct_size != sizeof(selenite_tx_cw_config) || f->reserved != 0 || f->side_mix > 1u || f->ns_taps == 0 || !f->shape_coeffs ||
+        !std::isfinite(f->amplitude) || !std::isfinite(f->side_level))
+        return SELENITE_RX_ARGUMENT_ERROR;                  // the previous setting stays
+    float sum = 0.0f;                                       // e[n] of a window that is all key-down: the taps in the FIR's own order
+    for (uint32_t k = 0; k < f->ns_taps; ++k) {
+        if (!std::isfinite(f->shape_coeffs[k])) return SELENITE_RX_ARGUMENT_ERROR;
+        sum = sum + f->shape_coeffs[k];
+    }
+    const size_t C = S->cfg.channels, ns1 = f->ns_taps - 1;
+    const bool first = !W.set, new_len = first || f->ns_taps != W.p.ns;
+    if (int rc = drain(S)) return rc;
+    for (uint32_t **row : { &W.d_side_step, &W.d_side_phase, &W.d_tx_on, &W.d_hold })
+        if (!*row) HIPCHK(S, dev_alloc(row, C));
+    // what depends on ns_taps is allocated before anything of the previous setting is given up
+    float *shape = W.d_shape;
+    uint8_t *ks = W.d_key_state;
+    if (new_len || !shape) {
+        HIPCHK(S, dev_alloc(&shape, (size_t)f->ns_taps));
+        if (dev_alloc(&ks, C * ns1) != hipSuccess) {
+            (void)hipFree(shape);
+            return fail(S, SELENITE_RX_DEVICE_ERROR, "hipMalloc(key_state)");
+        }
+    }
+    if (shape != W.d_shape) {
+        dev_free(W.d_shape, W.d_key_state);
+        W.d_shape = shape; W.d_key_state = ks;
+    }
+    std::vector<uint32_t> ss(C);
+    for (size_t c = 0; c < C; ++c) ss[c] = f->side_step ? f->side_step[c] : f->side_step_all;
+    HIPCHK(S, hipMemcpy(W.d_shape, f->shape_coeffs, f->ns_taps * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(S, hipMemcpy(W.d_side_step, ss.data(), C * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (new_len && ns1) HIPCHK(S, hipMemset(W.d_key_state, 0, C * ns1));
+    if (first)                                              // a retune keeps the sidetone's phase and the break-in state
+        for (uint32_t *row : { W.d_side_phase, W.d_tx_on, W.d_hold }) HIPCHK(S, hipMemset(row, 0, C * sizeof(uint32_t)));
+    W.p = TxCwParams{ f->ns_taps, W.d_shape, sum, f->amplitude, f->side_level, f->offset_step, f->side_mix, f->hang_blocks,
+                      W.d_side_step, W.d_side_phase, W.d_tx_on, W.d_hold, W.d_key_state };
+    W.set = true;
+    return SELENITE_RX_SUCCESS;
+}
+
+extern "C" int selenite_tx_get_cw_state(selenite_tx_instance *S, const selenite_tx_cw_state_view *v) { return cw_state_copy(S, v, true); }
+extern "C" int selenite_tx_set_cw_state(selenite_tx_instance *S, const selenite_tx_cw_state_view *v) { return cw_state_copy(S, v, false); }
+
+extern "C" int selenite_tx_process_key_f32_device(selenite_tx_instance *S, const uint8_t *key, float *dst, float *side, uint32_t bs) { return process_key_device(S, key, dst, side, bs, false, "selenite_tx_process_key_f32_device"); }
+extern "C" int selenite_tx_process_key_q15_device(selenite_tx_instance *S, const uint8_t *key, int16_t *dst, int16_t *side, uint32_t bs) { return process_key_device(S, key, dst, side, bs, true, "selenite_tx_process_key_q15_device"); }
+extern "C" int selenite_tx_process_key_f32(selenite_tx_instance *S, const uint8_t *key, float *dst, float *side, uint32_t bs) { return process_key_host(S, key, dst, side, bs, false, "selenite_tx_process_key_f32"); }
+extern "C" int selenite_tx_process_key_q15(selenite_tx_instance *S, const uint8_t *key, int16_t *dst, int16_t *side, uint32_t bs) { return process_key_host(S, key, dst, side, bs, true, "selenite_tx_process_key_q15"); }
+
+extern "C" const uint32_t *selenite_tx_cw_txon_device(selenite_tx_instance *S) { return (S && S->cw.set) ? S->cw.d_tx_on : nullptr; }
+
+extern "C" int selenite_tx_time_process_key_device(selenite_tx_instance *S, const uint8_t *key, float *dst, float *side, uint32_t bs,
+                                                   uint32_t iters, float *ms_per_call)
+{
+    if (!S || !ms_per_call || iters == 0) return SELENITE_RX_ARGUMENT_ERROR;
+    if (int r = key_call_ok(S, key, dst, bs, "selenite_tx_time_process_key_device")) return r;
+    return timed_loop(S, iters, ms_per_call, [&] { return run_key(S, key, dst, side, false, bs); });
+}

@@ -6,11 +6,13 @@
 // wave-wide prefix scan of (uint32)d[n] + step gives the bits of the sequential loop; everything in front of it is k_tx_generic's
 // chain on one rail (same per-output accumulation order: one accumulator from +0.0f, taps ascending), two outputs per packed MAC.
 // One single-wave workgroup per channel, ALC block by ALC block, 64 outputs per scan slice.
+// Kernel, launcher and the host side of the mode: selenite_tx_set_fm and the tone's state accessors.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 
 #include "rx_device.h"
-#include "tx_internal.h"
+#include "tx_host.h"
 
 namespace srx {
 
@@ -253,4 +255,51 @@ hipError_t launch_tx_fm(const TxParams &p, const TxFmParams &f, int arith, const
     return fma ? launch_fm<1, float, float>(p, f, src, dst, st) : launch_fm<0, float, float>(p, f, src, dst, st);
 }
 
+// ---- the host side (tx_host.h) ----
+
+void tx_fm_free(selenite_tx_instance *S) { dev_free(S->fm.d_tone_step, S->fm.d_tone_phase); }
+
+int tx_fm_reset(selenite_tx_instance *S)
+{
+    if (S->fm.d_tone_phase) HIPCHK(S, hipMemsetAsync(S->fm.d_tone_phase, 0, S->cfg.channels * sizeof(uint32_t), S->stream));
+    return 0;
+}
+
+static int fm_state_copy(selenite_tx_instance *S, const selenite_tx_fm_state_view *v, bool to_host)
+{
+    if (!S || !v || !S->fm.set) return SELENITE_RX_ARGUMENT_ERROR;
+    return copy_rows(S, to_host, { { S->fm.d_tone_phase, v->tone_phase, S->cfg.channels * sizeof(uint32_t) } });
+}
+
 }  // namespace srx
+
+using namespace srx;
+
+extern "C" int selenite_tx_set_fm(selenite_tx_instance *S, const selenite_tx_fm_config *f)
+{
+    if (!S) return SELENITE_RX_ARGUMENT_ERROR;
+    static_assert(sizeof(selenite_tx_fm_config) == 40 && offsetof(selenite_tx_fm_config, tone_step) == 24, "selenite_tx_fm_config layout (LP64)");
+    selenite_tx_instance::Fm &F = S->fm;
+    if (!f) {                                               // FM off again: not from under a running FM mode
+        if (S->cfg.mode == SELENITE_MODE_FM) return SELENITE_RX_ARGUMENT_ERROR;
+        F.set = false;
+        return SELENITE_RX_SUCCESS;
+    }
+    if (f->struct_size != sizeof(selenite_tx_fm_config) || f->reserved != 0 || f->tone_enable > 1u ||
+        !std::isfinite(f->deviation) || !(f->deviation > 0.0f) || !std::isfinite(f->amplitude) || !std::isfinite(f->tone_level))
+        return SELENITE_RX_ARGUMENT_ERROR;                  // the previous setting stays
+    const size_t C = S->cfg.channels;
+    if (int rc = drain(S)) return rc;
+    if (!F.d_tone_step) HIPCHK(S, dev_alloc(&F.d_tone_step, C));
+    if (!F.d_tone_phase) HIPCHK(S, dev_alloc(&F.d_tone_phase, C));
+    std::vector<uint32_t> ts(C);
+    for (size_t c = 0; c < C; ++c) ts[c] = f->tone_step ? f->tone_step[c] : f->tone_step_all;
+    HIPCHK(S, hipMemcpy(F.d_tone_step, ts.data(), C * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!F.set) HIPCHK(S, hipMemset(F.d_tone_phase, 0, C * sizeof(uint32_t)));       // a retune keeps the tone's phase
+    F.p = TxFmParams{ f->deviation, f->amplitude, f->tone_level, f->tone_enable, F.d_tone_step, F.d_tone_phase };
+    F.set = true;
+    return SELENITE_RX_SUCCESS;
+}
+
+extern "C" int selenite_tx_get_fm_state(selenite_tx_instance *S, const selenite_tx_fm_state_view *v) { return fm_state_copy(S, v, true); }
+extern "C" int selenite_tx_set_fm_state(selenite_tx_instance *S, const selenite_tx_fm_state_view *v) { return fm_state_copy(S, v, false); }

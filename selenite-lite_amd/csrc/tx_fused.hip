@@ -16,6 +16,7 @@
 
 #include "rx_internal.h"
 #include "tx_internal.h"
+#include "tx_select.h"
 #include <cstdlib>
 
 namespace srx {
@@ -25,6 +26,8 @@ namespace {
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 constexpr int kL = 4, kNI = 256, kP = kNI / kL, kNH = 63, kBlk = 64, kPass = 256;
+static_assert(kL == kTxFusedL && kNI == kTxFusedNI && kNH == kTxFusedNH && kBlk == kTxFusedBlock && kPass == kTxFusedPass,
+              "tx_select.h decides for the shape these kernels are written for");
 constexpr int kHH = kNH - 1, kHH4 = (kHH + 3) & ~3, kFH = kHH4 - kHH;        // Hilbert history 62 -> 64, lead pad 2
 constexpr int kHLen = kHH4 + kPass + 4;
 constexpr int kZH = 64;                                                       // interpolator history slots (63 used)
@@ -570,7 +573,7 @@ __global__ __launch_bounds__(64, 2) void k_tx_split16(TxParams p, uint32_t delay
 }
 
 template <typename TIn, typename TOut>
-hipError_t launch_s16(const TxParams &p, uint32_t delay_idx, const float2 *lo, const void *ttab16, int tap_sc, const void *src,
+hipError_t launch_s16(const TxParams &p, uint32_t nco, uint32_t delay_idx, const float2 *lo, const void *ttab16, int tap_sc, const void *src,
                       void *dst, hipStream_t st)
 {
     constexpr size_t lds = (size_t)(kTotal16 + 2 * kPass * kL) * sizeof(float);      // + the 8 KB output tile
@@ -589,33 +592,33 @@ hipError_t launch_s16(const TxParams &p, uint32_t delay_idx, const float2 *lo, c
     const dim3 grid(resident > 0 && (uint32_t)resident < p.channels ? (uint32_t)resident : p.channels), blk(64);
     const TIn *s = static_cast<const TIn *>(src);
     TOut *d = static_cast<TOut *>(dst);
-    if (!p.nco) hipLaunchKernelGGL((k_tx_split16<0, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, ttab16, tap_sc, s, d);
-    else if (lo && p.lo_period == 256) hipLaunchKernelGGL((k_tx_split16<3, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, ttab16, tap_sc, s, d);
-    else if (lo) hipLaunchKernelGGL((k_tx_split16<2, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, ttab16, tap_sc, s, d);
-    else hipLaunchKernelGGL((k_tx_split16<1, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, ttab16, tap_sc, s, d);
+    switch (nco) {
+    case 0: hipLaunchKernelGGL((k_tx_split16<0, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, ttab16, tap_sc, s, d); break;
+    case 1: hipLaunchKernelGGL((k_tx_split16<1, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, ttab16, tap_sc, s, d); break;
+    case 2: hipLaunchKernelGGL((k_tx_split16<2, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, ttab16, tap_sc, s, d); break;
+    case 3: hipLaunchKernelGGL((k_tx_split16<3, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, ttab16, tap_sc, s, d); break;
+    default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
 template <int ARITH, typename TIn, typename TOut>
-hipError_t launch_a(const TxParams &p, uint32_t delay_idx, const float2 *lo, const void *src, void *dst, hipStream_t st)
+hipError_t launch_a(const TxParams &p, uint32_t nco, uint32_t delay_idx, const float2 *lo, const void *src, void *dst, hipStream_t st)
 {
     constexpr size_t lds = (size_t)kTotal * sizeof(float);
     const dim3 grid(p.channels), blk(64);
     const TIn *s = static_cast<const TIn *>(src);
     TOut *d = static_cast<TOut *>(dst);
-    if (!p.nco) hipLaunchKernelGGL((k_tx_fused<ARITH, 0, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, s, d);
-    else if (lo) hipLaunchKernelGGL((k_tx_fused<ARITH, 2, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, s, d);
-    else hipLaunchKernelGGL((k_tx_fused<ARITH, 1, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, s, d);
+    switch (nco) {
+    case 0: hipLaunchKernelGGL((k_tx_fused<ARITH, 0, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, s, d); break;
+    case 1: hipLaunchKernelGGL((k_tx_fused<ARITH, 1, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, s, d); break;
+    case 2: hipLaunchKernelGGL((k_tx_fused<ARITH, 2, TIn, TOut>), grid, blk, lds, st, p, delay_idx, lo, s, d); break;
+    default: return hipErrorInvalidValue;             // (3: k_tx_split16 only)
+    }
     return hipGetLastError();
 }
 
 }  // namespace
-
-bool tx_fused_ok(const selenite_tx_config &g, bool delay_is_impulse, bool hilb_odd_only, uint32_t block_size)
-{
-    return g.interp == kL && g.ni_taps == kNI && g.nh_taps == kNH && g.block == kBlk && delay_is_impulse &&
-           hilb_odd_only && block_size % kPass == 0;
-}
 
 // Toeplitz fragments of the four interpolator phases for k_tx_split16 (f16 hi / lo, taps x 2^SC);
 // *tap_sc = SC.  Layout: [phase][k-step][hi, lo][lane][8 halfs].
@@ -646,19 +649,19 @@ hipError_t build_tx_split16_table(const float *interp_coeffs, void **d_table, in
     return e;
 }
 
-hipError_t launch_tx_split16(const TxParams &p, uint32_t delay_idx, const float2 *lo, const void *ttab16, int tap_sc,
+hipError_t launch_tx_split16(const TxParams &p, uint32_t nco, uint32_t delay_idx, const float2 *lo, const void *ttab16, int tap_sc,
                              const void *src, bool q15, void *dst, hipStream_t st)
 {
-    return q15 ? launch_s16<int16_t, int16_t>(p, delay_idx, lo, ttab16, tap_sc, src, dst, st)
-               : launch_s16<float, float>(p, delay_idx, lo, ttab16, tap_sc, src, dst, st);
+    return q15 ? launch_s16<int16_t, int16_t>(p, nco, delay_idx, lo, ttab16, tap_sc, src, dst, st)
+               : launch_s16<float, float>(p, nco, delay_idx, lo, ttab16, tap_sc, src, dst, st);
 }
 
-hipError_t launch_tx_fused(const TxParams &p, int arith, uint32_t delay_idx, const float2 *lo, const void *src, bool q15,
+hipError_t launch_tx_fused(const TxParams &p, int arith, uint32_t nco, uint32_t delay_idx, const float2 *lo, const void *src, bool q15,
                            void *dst, hipStream_t st)
 {
     if (arith != SELENITE_ARITH_CMSIS)
-        return q15 ? launch_a<1, int16_t, int16_t>(p, delay_idx, lo, src, dst, st) : launch_a<1, float, float>(p, delay_idx, lo, src, dst, st);
-    return q15 ? launch_a<0, int16_t, int16_t>(p, delay_idx, lo, src, dst, st) : launch_a<0, float, float>(p, delay_idx, lo, src, dst, st);
+        return q15 ? launch_a<1, int16_t, int16_t>(p, nco, delay_idx, lo, src, dst, st) : launch_a<1, float, float>(p, nco, delay_idx, lo, src, dst, st);
+    return q15 ? launch_a<0, int16_t, int16_t>(p, nco, delay_idx, lo, src, dst, st) : launch_a<0, float, float>(p, nco, delay_idx, lo, src, dst, st);
 }
 
 }  // namespace srx

@@ -1,6 +1,6 @@
 // tx_in.hip -- the audio input stage of the batched TX chain (include/selenite_tx_in.h: selenite_tx_set_in; DESIGN.md section 2 "TX input",
 // section 5.18).  Slot-rate frames (f32 or int16, mono or interleaved left / right) -> pick / mix -> mic gain -> arm_fir_decimate_f32 by M
-// -> VOX per DSP block -> gate -> the chain's audio (f32 or int16) in a buffer of the instance, on which run() of tx.hip then works.
+// -> VOX per DSP block -> gate -> the chain's audio (f32 or int16) in a buffer of the instance, on which run() of tx_api.hip then works.
 //
 // k_out's mirror image (rx_out.hip): no recurrence, a streaming kernel, one single-wave workgroup per channel row.  The row streams through
 // LDS in tiles of whole DSP blocks (about 1024 input samples) behind nt - 1 samples of history -- the first tile's history is the channel's
@@ -25,10 +25,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cfloat>
+#include <cmath>
 
 #include "../../include/selenite_tx.h"
 #include "rx_device.h"
-#include "tx_internal.h"
+#include "tx_host.h"
 
 namespace srx {
 
@@ -374,4 +375,168 @@ hipError_t launch_tx_in(const TxInParams &q, const void *frames, bool in_q15, vo
     return hipErrorInvalidValue;
 }
 
+// ---- the host side (tx_host.h): selenite_tx_set_in, the stage's state accessors, the frame entries ----
+
+void tx_in_free(selenite_tx_instance *S)
+{
+    selenite_tx_instance::In &I = S->in;
+    dev_free(I.d_coeffs, I.d_dec, I.d_level, I.d_open, I.d_hold, I.d_opens, I.d_open_blocks, I.d_audio);
+}
+
+// the stage's state as the first selenite_tx_set_in leaves it: the decimator tail +0.0f and, with `vox`, level_init, closed, counters 0
+static int in_clear_state(selenite_tx_instance *S, bool vox)
+{
+    const selenite_tx_instance::In &I = S->in;
+    const size_t C = S->cfg.channels, h1 = I.p.nt ? I.p.nt - 1 : 0;
+    if (h1) HIPCHK(S, hipMemsetAsync(I.d_dec, 0, C * h1 * sizeof(float), S->stream));
+    if (!vox) return drain(S);
+    for (uint32_t *row : { I.d_open, I.d_hold }) HIPCHK(S, hipMemsetAsync(row, 0, C * sizeof(uint32_t), S->stream));
+    for (uint64_t *row : { I.d_opens, I.d_open_blocks }) HIPCHK(S, hipMemsetAsync(row, 0, C * sizeof(uint64_t), S->stream));
+    return fill_rows(S, I.d_level, C, &I.level_init);      // (drains the stream)
+}
+
+int tx_in_reset(selenite_tx_instance *S) { return S->in.set ? in_clear_state(S, true) : 0; }
+
+static TxInParams in_params(const selenite_tx_instance *S, uint32_t bs)
+{
+    TxInParams q = S->in.p;
+    q.channels = S->cfg.channels; q.block = S->cfg.block; q.block_size = bs; q.q15_round = S->cfg.q15_rounding ? 1u : 0u;
+    return q;
+}
+
+// frame calls: every refusal comes before anything is written, what run() would refuse behind the stage included
+static int frames_call_ok(selenite_tx_instance *S, const void *frames, const void *dst, uint32_t bs, const char *who)
+{
+    if (!S) return SELENITE_RX_ARGUMENT_ERROR;
+    if (!S->in.set) return fail(S, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": the input stage is not configured (selenite_tx_set_in)");
+    if (!frames || !dst) return fail(S, SELENITE_RX_ARGUMENT_ERROR, std::string(who) + ": NULL buffer");
+    if (!block_size_ok(S, bs, who)) return SELENITE_RX_LENGTH_ERROR;
+    if (tx_in_lds_bytes(in_params(S, bs)) > kTxLdsLimit || decide(S, make_params(S, bs), false).refused)
+        return fail(S, SELENITE_RX_LENGTH_ERROR, std::string(who) + ": the layout exceeds the LDS budget of a TX kernel");
+    return 0;
+}
+
+static int run_in_stage(selenite_tx_instance *S, const void *frames, bool in_q15, bool out_q15, uint32_t bs)
+{
+    HIPCHK(S, hipSetDevice(S->device));
+    if (ensure(S, &S->in.d_audio, &S->in.audio_bytes, (size_t)S->cfg.channels * bs * sample_bytes(out_q15))) return S->status;
+    HIPCHK(S, launch_tx_in(in_params(S, bs), frames, in_q15, S->in.d_audio, out_q15, S->stream));
+    return 0;
+}
+
+static int run_frames(selenite_tx_instance *S, const void *frames, bool in_q15, void *dst, bool out_q15, uint32_t bs)
+{
+    if (int r = run_in_stage(S, frames, in_q15, out_q15, bs)) return r;
+    return run(S, S->in.d_audio, dst, out_q15, bs);              // the existing chain on the stage's audio, unchanged
+}
+
+static int process_frames_device(selenite_tx_instance *S, const void *frames, bool in_q15, void *dst, bool out_q15, uint32_t bs, const char *who)
+{
+    if (int r = frames_call_ok(S, frames, dst, bs, who)) return r;
+    return run_frames(S, frames, in_q15, dst, out_q15, bs);
+}
+
+static int process_frames_host(selenite_tx_instance *S, const void *frames, void *dst, uint32_t bs, bool q15, const char *who)
+{
+    if (int r = frames_call_ok(S, frames, dst, bs, who)) return r;
+    const size_t fw = S->in.p.pick == SELENITE_TX_IN_MONO ? 1 : 2, na = (size_t)S->cfg.channels * bs * sample_bytes(q15);
+    return staged_call(S, { { frames, na * S->in.p.M * fw, kToDevice, &S->d_io_in, &S->io_in_bytes },
+                            { dst, na * S->cfg.interp * 2, kToHost, &S->d_io_out, &S->io_out_bytes } },
+                       [&] { return run_frames(S, S->d_io_in, q15, S->d_io_out, q15, bs); });
+}
+
+static int in_state_copy(selenite_tx_instance *S, const selenite_tx_in_state_view *v, bool to_host)
+{
+    if (!S || !v || !S->in.set) return SELENITE_RX_ARGUMENT_ERROR;
+    const selenite_tx_instance::In &I = S->in;
+    const size_t C = S->cfg.channels, h1 = I.p.nt ? I.p.nt - 1 : 0;
+    return copy_rows(S, to_host, { { I.d_dec, v->dec_state, C * h1 * sizeof(float) }, { I.d_level, v->level, C * sizeof(float) },
+                                   { I.d_open, v->open, C * sizeof(uint32_t) }, { I.d_hold, v->hold, C * sizeof(uint32_t) },
+                                   { I.d_opens, v->opens, C * sizeof(uint64_t) }, { I.d_open_blocks, v->open_blocks, C * sizeof(uint64_t) } });
+}
+
 }  // namespace srx
+
+using namespace srx;
+
+extern "C" int selenite_tx_set_in(selenite_tx_instance *S, const selenite_tx_in_config *f)
+{
+    if (!S) return SELENITE_RX_ARGUMENT_ERROR;
+    static_assert(sizeof(selenite_tx_in_config) == 72 && offsetof(selenite_tx_in_config, coeffs) == 16 && offsetof(selenite_tx_in_config, meter) == 32 &&
+                  sizeof(selenite_tx_in_state_view) == 48, "selenite_tx_in_config layout (LP64)");
+    selenite_tx_instance::In &I = S->in;
+    if (!f) {                                               // the stage off again, in any mode: the audio and key entries never needed it
+        I.set = false;
+        return SELENITE_RX_SUCCESS;
+    }
+    if (f->struct_size != sizeof(selenite_tx_in_config) || f->reserved != 0 || !(f->M == 1 || f->M == 2 || f->M == 4 || f->M == 8) ||
+        f->nd_taps > 256 || (f->nd_taps == 0 && f->M != 1) || (f->nd_taps && !f->coeffs) || f->pick > SELENITE_TX_IN_MIX ||
+        !std::isfinite(f->gain) || f->vox > 1u)
+        return SELENITE_RX_ARGUMENT_ERROR;                  // the previous setting stays
+    for (uint32_t k = 0; k < f->nd_taps; ++k)
+        if (!std::isfinite(f->coeffs[k])) return SELENITE_RX_ARGUMENT_ERROR;
+    const selenite_rx_meter_config &m = f->meter;
+    if (f->vox) {                                           // selenite_rx_set_meter's own rules, sense ABOVE
+        if (m.struct_size != sizeof(selenite_rx_meter_config) || m.sense != SELENITE_RX_SQ_ABOVE || m.gate > 1u || m.hang > 65535u ||
+            !(m.attack > 0.0f && m.attack <= 1.0f) || !(m.decay > 0.0f && m.decay <= 1.0f) ||
+            !(std::isfinite(m.open_level) && m.open_level >= 0.0f) || !(std::isfinite(m.close_level) && m.close_level >= 0.0f) ||
+            !(m.close_level <= m.open_level) || !(std::isfinite(m.level_init) && m.level_init >= 0.0f))
+            return SELENITE_RX_ARGUMENT_ERROR;
+    }
+    const size_t C = S->cfg.channels, h1 = f->nd_taps ? f->nd_taps - 1 : 0;
+    const bool first = !I.set, new_len = first || f->nd_taps != I.p.nt;
+    if (int rc = drain(S)) return rc;
+    if (!I.d_level) HIPCHK(S, dev_alloc(&I.d_level, C));
+    for (uint32_t **row : { &I.d_open, &I.d_hold })
+        if (!*row) HIPCHK(S, dev_alloc(row, C));
+    for (uint64_t **row : { &I.d_opens, &I.d_open_blocks })
+        if (!*row) HIPCHK(S, dev_alloc(row, C));
+    if (new_len) {                                          // what depends on nd_taps is allocated before anything of the previous setting is given up
+        float *coeffs = nullptr, *dec = nullptr;
+        HIPCHK(S, dev_alloc(&coeffs, (size_t)f->nd_taps));
+        if (dev_alloc(&dec, C * h1) != hipSuccess) {
+            (void)hipFree(coeffs);
+            return fail(S, SELENITE_RX_DEVICE_ERROR, "hipMalloc(dec_state)");
+        }
+        dev_free(I.d_coeffs, I.d_dec);
+        I.d_coeffs = coeffs; I.d_dec = dec;
+    }
+    if (f->nd_taps) HIPCHK(S, hipMemcpy(I.d_coeffs, f->coeffs, f->nd_taps * sizeof(float), hipMemcpyHostToDevice));
+    TxInParams q{};
+    q.M = f->M; q.nt = f->nd_taps; q.pick = f->pick; q.gain = f->gain; q.vox = f->vox;
+    if (f->vox) {
+        q.gate = m.gate; q.hang = m.hang; q.attack = m.attack; q.decay = m.decay; q.open_level = m.open_level; q.close_level = m.close_level;
+        I.level_init = m.level_init;
+    }
+    q.coeffs = I.d_coeffs; q.dec_state = I.d_dec; q.level = I.d_level; q.open = I.d_open; q.hold = I.d_hold;
+    q.opens = I.d_opens; q.open_blocks = I.d_open_blocks;
+    I.p = q;
+    if (new_len) {                                          // a retune keeps the decimator tail (same nd_taps) and the VOX state
+        if (first && !f->vox) I.level_init = 0.0f;
+        if (in_clear_state(S, first)) return S->status;
+    }
+    I.set = true;
+    return SELENITE_RX_SUCCESS;
+}
+
+extern "C" int selenite_tx_get_in_state(selenite_tx_instance *S, const selenite_tx_in_state_view *v) { return in_state_copy(S, v, true); }
+extern "C" int selenite_tx_set_in_state(selenite_tx_instance *S, const selenite_tx_in_state_view *v) { return in_state_copy(S, v, false); }
+
+extern "C" int selenite_tx_process_frames_f32_device(selenite_tx_instance *S, const float *frames, float *dst, uint32_t bs) { return process_frames_device(S, frames, false, dst, false, bs, "selenite_tx_process_frames_f32_device"); }
+extern "C" int selenite_tx_process_frames_q15_device(selenite_tx_instance *S, const int16_t *frames, int16_t *dst, uint32_t bs) { return process_frames_device(S, frames, true, dst, true, bs, "selenite_tx_process_frames_q15_device"); }
+extern "C" int selenite_tx_process_frames_q15_f32_device(selenite_tx_instance *S, const int16_t *frames, float *dst, uint32_t bs) { return process_frames_device(S, frames, true, dst, false, bs, "selenite_tx_process_frames_q15_f32_device"); }
+extern "C" int selenite_tx_process_frames_f32(selenite_tx_instance *S, const float *frames, float *dst, uint32_t bs) { return process_frames_host(S, frames, dst, bs, false, "selenite_tx_process_frames_f32"); }
+extern "C" int selenite_tx_process_frames_q15(selenite_tx_instance *S, const int16_t *frames, int16_t *dst, uint32_t bs) { return process_frames_host(S, frames, dst, bs, true, "selenite_tx_process_frames_q15"); }
+
+extern "C" const uint32_t *selenite_tx_in_vox_device(selenite_tx_instance *S) { return (S && S->in.set) ? S->in.d_open : nullptr; }
+extern "C" const void *selenite_tx_in_audio_device(selenite_tx_instance *S) { return (S && S->in.set) ? S->in.d_audio : nullptr; }
+
+extern "C" int selenite_tx_time_in_stage_device(selenite_tx_instance *S, const void *frames, uint32_t kind, uint32_t bs, uint32_t iters,
+                                                float *ms_per_launch)
+{
+    if (!S || !ms_per_launch || iters == 0 || kind > SELENITE_TX_IN_Q15_F32) return SELENITE_RX_ARGUMENT_ERROR;
+    if (int r = frames_call_ok(S, frames, ms_per_launch, bs, "selenite_tx_time_in_stage_device")) return r;
+    const bool in_q15 = kind != SELENITE_TX_IN_F32, out_q15 = kind == SELENITE_TX_IN_Q15;
+    // (the untimed first launch grows the audio buffer outside the timed span)
+    return timed_loop(S, iters, ms_per_launch, [&] { return run_in_stage(S, frames, in_q15, out_q15, bs); }, true);
+}

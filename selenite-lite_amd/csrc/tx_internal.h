@@ -1,4 +1,5 @@
-// tx_internal.h -- kernel parameter block and launch interfaces shared by tx.hip, tx_fused.hip and tx_fm.hip.
+// tx_internal.h -- kernel parameter blocks and launch interfaces of the TX kernels' files (tx_generic.hip, tx_fused.hip, tx_fm.hip,
+// tx_cw.hip, tx_in.hip), as tx_api.hip and the stages' host sides call them.
 // Not part of the C-ABI (include/selenite_tx.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,16 +23,18 @@ struct TxParams {
     AgcParams alcp;
 };
 
-// tx_fused.hip: the BASELINE-like shape (ALC block 64, L = 4, 256-tap interpolator, 63-tap Hilbert
-// pair with a unit-impulse delay and a type-III Hilbert).  `lo` = shared LO of the call as produced by
-// launch_lo_table (cos, -sin) or NULL (per-channel NCO in the kernel).
-bool tx_fused_ok(const selenite_tx_config &g, bool delay_is_impulse, bool hilb_odd_only, uint32_t block_size);
-hipError_t launch_tx_fused(const TxParams &p, int arith, uint32_t delay_idx, const float2 *lo, const void *src, bool q15,
+// tx_generic.hip: k_tx_generic<ARITH, TIn, TOut>, any shape whose layout fits the LDS
+size_t tx_lds_bytes(const TxParams &p);
+hipError_t launch_tx_generic(const TxParams &p, int arith, const void *src, bool q15, void *dst, hipStream_t st);
+
+// tx_fused.hip: the BASELINE-like shape (tx_select.h: tx_fused_ok).  `nco` = the flavour the decision names (TxDecision::nco);
+// `lo` = shared LO of the call as produced by launch_lo_table (cos, -sin), read by flavours 2 and 3.
+hipError_t launch_tx_fused(const TxParams &p, int arith, uint32_t nco, uint32_t delay_idx, const float2 *lo, const void *src, bool q15,
                            void *dst, hipStream_t st);
 
 // SELENITE_ARITH_SPLIT16: the interpolator on the 16-bit matrix pipe (k_tx_split16), same shape as the fused kernel
 hipError_t build_tx_split16_table(const float *interp_coeffs, void **d_table, int *tap_sc);
-hipError_t launch_tx_split16(const TxParams &p, uint32_t delay_idx, const float2 *lo, const void *ttab16, int tap_sc,
+hipError_t launch_tx_split16(const TxParams &p, uint32_t nco, uint32_t delay_idx, const float2 *lo, const void *ttab16, int tap_sc,
                              const void *src, bool q15, void *dst, hipStream_t st);
 
 // tx_fm.hip: SELENITE_MODE_FM (selenite_tx_set_fm).  k_tx_fm<ARITH, TIn, TOut>: any shape k_tx_generic serves, one single-wave

@@ -26,10 +26,10 @@ The call sites (grep -n "agc_update\\|agc_desired\\|agc_step" selenite-lite_amd/
   rx_generic.hip:448             k_agc_apply_global, chunked      test_global_gain_apply_forms[cfg3_64]: the calls of 256 / 512 (64 / 128 outputs); int16 out: test_global_gain_other_routes[int16]
   rx_generic.hip:455             k_agc_apply_global, strided      test_global_gain_apply_forms[wide]: na = 512, 128 float4 per block
   rx_generic.hip:467             k_agc_apply_global, scalar       test_global_gain_apply_forms[na14]: na = 14
-  tx.hip:128                     k_tx_generic                     test_tx_kernel_forms[generic]
-  tx_fused.hip:140 / :144        k_tx_fused                       test_tx_kernel_forms[fused-cmsis / fused-fma], f32 and int16
-  tx_fused.hip:393 / :397        k_tx_split16                     test_tx_kernel_forms[split16], f32 and int16
-The seven parameters reach them through make_params (rx_dispatch.hip:75) / tx.hip:245, the initial gain through rx_api.hip:122 / tx.hip:331
+  tx_generic.hip:94              k_tx_generic                     test_tx_kernel_forms[generic]
+  tx_fused.hip:143 / :147        k_tx_fused                       test_tx_kernel_forms[fused-cmsis / fused-fma], f32 and int16
+  tx_fused.hip:408 / :412        k_tx_split16                     test_tx_kernel_forms[split16], f32 and int16
+The seven parameters reach them through make_params (rx_dispatch.hip:75) / tx_api.hip:28, the initial gain through rx_api.hip:102 / tx_api.hip:94
 (init and reset) and, for a host-pointer call cut into channel chunks, through the chunk's channel range: test_host_call_in_ragged_channel_chunks,
 test_reset_returns_to_the_configured_gain.
 

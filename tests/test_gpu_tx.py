@@ -1,4 +1,4 @@
-"""GPU: the TX chain (include/selenite_tx.h, csrc/tx.hip) through the C-ABI against the oracle
+"""GPU: the TX chain (include/selenite_tx.h, csrc/tx_api.hip, tx_generic.hip, tx_fused.hip) through the C-ABI against the oracle
 (oracle/tx_oracle.c, pinned against real CMSIS-DSP in tests/test_tx_oracle.py) and the committed
 fixtures produced by the real-CMSIS composition.  Bit-exact in both arithmetic modes (the FMA mode
 against the oracle's fmaf restatement), and within 1e-5 relative of the CMSIS arithmetic."""

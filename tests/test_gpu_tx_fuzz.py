@@ -1,4 +1,4 @@
-"""GPU: random configurations and call sequences of the TX chain (csrc/tx.hip: run() -- k_tx_generic, k_tx_fused, k_tx_split16, k_tx_fm)
+"""GPU: random configurations and call sequences of the TX chain (csrc/tx_api.hip: run(), as csrc/tx_select.h decides -- k_tx_generic, k_tx_fused, k_tx_split16, k_tx_fm)
 against the oracle (tests/txfm_oracle.py: TxFmOracle over oracle/tx_oracle.c), the counterpart of tests/test_gpu_fuzz.py for the RX side.
 
 tests/tx_fuzz_cases.py draws the cases: shapes (the fused geometry with designed, moved-impulse, odd-distance, dense and -0.0f taps; generic

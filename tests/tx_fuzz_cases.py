@@ -5,9 +5,10 @@ pasted into a directed test: the spec arguments, how the taps were overwritten, 
 makes the rc.TxSpec (taps overwritten as described), audio(case, event) the input of a call.  Every case has a random stream of its own
 (seed, kind, index), so case k of a kind is the same whatever n is.
 
-expected_kernel(case, mode) and walk(case) restate the HOST's rules (csrc/tx.hip: run(), selenite_tx_kernel_name, reset_state,
+expected_kernel(case, mode) and walk(case) restate the HOST's rules (csrc/tx_select.h: tx_select; csrc/tx_api.hip: run(), reset_state,
 selenite_tx_set_state): which kernel an instance reports, which kernel serves a call of a given length and from which phase source.  They
-read the taps the way selenite_tx_init classifies them.  tests/test_tx_fuzz_cases.py asserts on the CPU that the committed seed and counts
+read the taps the way selenite_tx_init classifies them.  This is the one restatement of the rule outside tx_select.h, kept deliberately
+as the independent check: tests/test_tx_select.py holds the C++ rule against it on every planned call of the committed cases.  tests/test_tx_fuzz_cases.py asserts on the CPU that the committed seed and counts
 reach every form, so coverage is a checked property of the generator.
 
 Kinds: "A" the fused geometry without FM events, "B" generic shapes without FM events, "FM" both families with an FM setting.
@@ -42,7 +43,7 @@ def scale_count(kind, env_value):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# LDS of the two any-shape kernels, in bytes (csrc/tx.hip: tx_layout, csrc/tx_fm.hip: fm_layout)
+# LDS of the two any-shape kernels, in bytes (csrc/tx_generic.hip: tx_layout, csrc/tx_fm.hip: fm_layout)
 # ---------------------------------------------------------------------------------------------------------------------------------------
 def _up4(v):
     return (v + 3) & ~3
@@ -313,7 +314,8 @@ def expected_kernel(case, mode=None):
 def walk(case):
     """(event index, record) for every planned call, a checkpoint's call twice.  record: kernel family that serves the call, its NCO
     flavour (off / table / periodic / perchan; FM: nco / zero_if), q15, device, mode, prev (the family of the call before), tags (what
-    the call is the first behind: reset_behind_fm, set_phase_behind_fm, restore_behind_fm), and the case's constants."""
+    the call is the first behind: reset_behind_fm, set_phase_behind_fm, restore_behind_fm), bs and uniform (the call's length and the
+    host's phase_uniform in front of it), and the case's constants."""
     s = case["spec"]
     steps = s["nco_steps"] if s["nco_steps"] is not None else [s["nco_step_all"]] * s["channels"]
     steps_same = len(set(steps)) == 1
@@ -325,7 +327,7 @@ def walk(case):
 
     def call(ev):
         nonlocal uniform, equal, dirty, prev, tags
-        bs = ev["blocks"] * s["block"]
+        bs, was_uniform = ev["blocks"] * s["block"], uniform
         if mode == FM:
             fam, flavour = "fm", "nco" if s["nco"] else "zero_if"
             uniform, equal, dirty = False, s["channels"] == 1, True
@@ -339,7 +341,7 @@ def walk(case):
                 flavour = "perchan"
         else:
             fam, flavour = "generic", "off" if not s["nco"] else "perchan"
-        rec = dict(kernel=fam, flavour=flavour, q15=ev["q15"], device=ev["device"], mode=mode, prev=prev, tags=frozenset(tags),
+        rec = dict(kernel=fam, flavour=flavour, q15=ev["q15"], device=ev["device"], mode=mode, prev=prev, tags=frozenset(tags), bs=bs, uniform=was_uniform,
                    steps_same=steps_same and s["nco"], arith=s["arith"], alc_set=s["alc_set"], tone=fm["tone"] if fm and mode == FM else None,
                    moved=case["taps"]["delay"][0] == "impulse" and case["taps"]["delay"][1] != 31)
         prev, tags = fam, set()

@@ -1,4 +1,4 @@
-"""Throughput of the TX chain (csrc/tx.hip): C channels x B audio samples per call -> C x 4B complex
+"""Throughput of the TX chain (csrc/tx_api.hip: run(); kernels in csrc/tx_generic.hip and csrc/tx_fused.hip): C channels x B audio samples per call -> C x 4B complex
 output samples, data resident in HBM, steady-state clocks.  Prints one JSON line.
 Algorithmic bytes per channel-call: 4*B audio in + 8*B*L I/Q out + state in and out."""
 import argparse

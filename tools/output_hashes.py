@@ -12,7 +12,12 @@ f32 and int16 slots, the device call, the host-pointer call, and with a global g
 (not with an output stage); audio + chain state + every stage's state.  Between the chain rows and these, the edge rows: calls at the
 edges of the rule that picks the kernel of a call (csrc/rx_select.h) -- short calls, partial passes, cut calls, the AUTO forms, FM, the
 dense flavour, the five LO situations, global gain, NLMS, the repair switched off, the generic path -- 33 channels, three calls each, with
-the kernel name, the NCO path and the form of the last AUTO launch beside the hash (`--chain-rows`: these and the chain rows, no child)."""
+the kernel name, the NCO path and the form of the last AUTO launch beside the hash (`--chain-rows`: these and the chain rows, no child).
+`--tx-rows`: the TX direction alone, in this process -- the fused geometry in `cmsis`, `fma` and `split16` with the NCO off, on the
+fs / 256 grid, on an odd step and with a step per channel; one generic shape (interp 3, 16-tap pair, block 65); FM with a tone; keyed CW
+with the sidetone mixed and stored, in CW and CWR; the input stage by 1 and 4, mono and mix, VOX gating -- f32 and int16, device and
+host entries, 5 channels and (matrix kernels) 130, three calls each with the middle one no whole number of passes, a state round-trip
+behind the first and a reset behind the second; outputs and every state array after every call, the kernel name beside each hash."""
 import hashlib
 import os
 import subprocess
@@ -253,7 +258,146 @@ def edge_rows():
         edge_row("cfg2 force-generic auto", cfg2(sr.ARITH_AUTO), 1024)
 
 
+def tx_rows():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rxcommon as rc                         # (TxSpec: the config builder the TX benches use)
+
+    def tone(n, bs, at, scale=0.5):
+        return np.ascontiguousarray(sr.synth_iq_host(0, n, at, bs, ch.SEED)[:, :, 0] * np.float32(scale))
+
+    def to_q15(x):
+        return np.clip(np.trunc(x * 32768.0), -32768, 32767).astype(np.int16)
+
+    def row(label, spec, lens, q15, device, setup=None, call=None, states=None):
+        """three calls; call(tx, k, at, bs) -> arrays to hash (default: the audio entries); states: (get, set) pairs besides the chain's"""
+        n, dt = spec.channels, np.int16 if q15 else np.float32
+        tx = sr.Tx(spec.config())
+        if setup:
+            setup(tx)
+        top = max(lens)
+        d_in, d_out = sr.DeviceBuffer(n * top * 8 * 4), sr.DeviceBuffer(n * top * spec.interp * 2 * 4)
+
+        def audio(tx, k, at, bs):
+            x = tone(n, bs, at)
+            x = to_q15(x) if q15 else x
+            if not device:
+                return [(tx.process_q15 if q15 else tx.process)(x)]
+            d_in.upload(x)
+            (tx.L.selenite_tx_process_q15_device if q15 else tx.L.selenite_tx_process_f32_device)(tx.h, d_in.ptr, d_out.ptr, bs)
+            tx.sync(); tx.check()
+            return [d_out.download((n, bs * spec.interp, 2), dt)]
+
+        states = ((tx.state, tx.set_state),) + (tuple(states(tx)) if states else ())
+        h, names, at = hashlib.sha256(), [], 0
+        for k, bs in enumerate(lens):
+            for y in (call or audio)(tx, k, at, bs, *(() if call is None else (d_in, d_out))):
+                h.update(np.ascontiguousarray(y).tobytes())
+            at += bs
+            for get, put in states:
+                st = get()
+                for key in sorted(st):
+                    h.update(np.ascontiguousarray(st[key]).tobytes())
+                if k == 0:
+                    put(st)                       # a state round-trip behind the first call,
+            if k == 1:
+                assert tx.reset() == 0            # a reset behind the second
+            names.append(tx.kernel_name())
+        tx.check()
+        print("tx", label, "x".join(map(str, lens)), n, "q15" if q15 else "f32", "device" if device else "host", "|", " ".join(names), "|", h.hexdigest()[:24])
+        tx.close(); d_in.free(); d_out.free()
+
+    def own(n):
+        return (np.arange(n, dtype=np.uint64) * 0x9E3779B1 % (1 << 32)).astype(np.uint32)
+
+    fmts = [(q15, device) for q15 in (False, True) for device in (True, False)]
+    los = [("lo-off", lambda n: dict(nco=False)), ("lo-grid", lambda n: dict(nco_step_all=GRID)), ("lo-odd", lambda n: dict(nco_step_all=OFFGRID)),
+           ("lo-own", lambda n: dict(nco_steps=own(n)))]
+    for tag, arith in (("cmsis", sr.ARITH_CMSIS), ("fma", sr.ARITH_FMA), ("split16", sr.ARITH_SPLIT16)):
+        for lo, kw in los:
+            for n in (5, 130):
+                for q15, device in fmts:          # fused -> generic -> fused on one instance
+                    row("fused %s %s" % (tag, lo), rc.TxSpec(n, arith=arith, **kw(n)), (512, 192, 256), q15, device)
+
+    def generic(n, arith, mode=sr.MODE_USB, **kw):
+        spec = rc.TxSpec(n, block=65, interp=3, ni_taps=48, nh_taps=0, mode=mode, arith=arith, **kw)
+        r = np.random.default_rng(16)
+        spec.nh_taps, spec.hilb, spec.delay = 16, r.uniform(-0.2, 0.2, 16).astype(np.float32), r.uniform(-0.2, 0.2, 16).astype(np.float32)
+        return spec
+
+    for tag, arith in (("cmsis", sr.ARITH_CMSIS), ("fma", sr.ARITH_FMA)):
+        for lo, kw in (los[0], los[3]):
+            for q15, device in fmts:
+                row("generic %s %s" % (tag, lo), generic(5, arith, **kw(5)), (130, 65, 195), q15, device)
+
+    def fm(tx):
+        assert tx.set_fm(deviation=0.2, amplitude=0.8, tone_level=0.1, tone_step=own(tx.cfg.channels) >> 6) == 0 and tx.set_mode(sr.MODE_FM) == 0
+    fm_states = lambda tx: ((tx.fm_state, tx.set_fm_state),)
+    for q15, device in fmts:
+        row("fm fused fma", rc.TxSpec(5, arith=sr.ARITH_FMA), (512, 192, 256), q15, device, fm, states=fm_states)
+        row("fm generic cmsis", generic(5, sr.ARITH_CMSIS), (130, 65, 195), q15, device, fm, states=fm_states)
+
+    def keyed(mix):
+        def setup(tx):
+            assert tx.set_cw(sr.keyshape(48), amplitude=0.9, offset_step=0x00300000, side_level=0.25, side_step=own(tx.cfg.channels) >> 4, side_mix=mix, hang_blocks=2) == 0
+        return setup
+
+    def key_call(q15, device):
+        def call(tx, k, at, bs, d_in, d_out):
+            n, dt = tx.cfg.channels, np.int16 if q15 else np.float32
+            key = (((np.arange(at, at + bs)[None, :] + 7 * np.arange(n)[:, None]) // 53) % 2).astype(np.uint8)
+            side = tone(n, bs, at, 0.25)
+            side = to_q15(side) if q15 else side
+            if not device:
+                rc_, iq, sd = tx.process_key_host(key, side, q15)
+                assert rc_ == 0
+                return [iq, sd]
+            d_side = sr.DeviceBuffer(side.nbytes)
+            d_in.upload(key); d_side.upload(side)
+            assert tx.process_key(d_in.ptr, d_out.ptr, d_side.ptr, bs, q15) == 0 and tx.sync() == 0
+            out = [d_out.download((n, bs * tx.cfg.interp, 2), dt), d_side.download((n, bs), dt)]
+            d_side.free()
+            return out
+        return call
+    cw_states = lambda tx: ((tx.cw_state, tx.set_cw_state),)
+    for mode, mtag in ((sr.MODE_CW, "cw"), (sr.MODE_CWR, "cwr")):
+        for mix in (0, 1):
+            for q15, device in fmts:
+                row("keyed %s side-%s" % (mtag, "mixed" if mix else "stored"), rc.TxSpec(5, mode=mode, arith=sr.ARITH_FMA), (512, 192, 256), q15, device,
+                    keyed(mix), key_call(q15, device), cw_states)
+
+    vox = dict(gate=1, hang=2, attack=0.5, decay=0.125, open_level=0.05, close_level=0.02, level_init=0.0)
+
+    def stage(M, pick):
+        def setup(tx):
+            assert tx.set_in(M=M, coeffs=sr.design_lowpass(32, 0.4 / M) if M > 1 else None, pick=pick, gain=0.9, vox=vox) == 0
+        return setup
+
+    def frame_call(M, pick, q15, device):
+        def call(tx, k, at, bs, d_in, d_out):
+            n, fw, dt = tx.cfg.channels, 1 if pick == sr.IN_MONO else 2, np.int16 if q15 else np.float32
+            gate = 1.0 if k != 1 else 0.01        # the middle call under the VOX threshold
+            fr = tone(n, bs * M * fw, at * M * fw, 0.5 * gate)
+            fr = to_q15(fr) if q15 else fr
+            if not device:
+                rc_, iq = tx.process_frames_host(fr, q15)
+                assert rc_ == 0
+                return [iq]
+            d_in.upload(fr)
+            assert tx.process_frames(d_in.ptr, d_out.ptr, bs, sr.IN_Q15 if q15 else sr.IN_F32) == 0 and tx.sync() == 0
+            return [d_out.download((n, bs * tx.cfg.interp, 2), dt)]
+        return call
+    in_states = lambda tx: ((tx.in_state, tx.set_in_state),)
+    for M in (1, 4):
+        for pick, ptag in ((sr.IN_MONO, "mono"), (sr.IN_MIX, "mix")):
+            for q15, device in fmts:
+                row("in by-%d %s vox" % (M, ptag), rc.TxSpec(5, arith=sr.ARITH_SPLIT16), (512, 192, 256), q15, device, stage(M, pick),
+                    frame_call(M, pick, q15, device), in_states)
+
+
 def main():
+    if sys.argv[1:] == ["--tx-rows"]:
+        tx_rows()
+        return 0
     if sys.argv[1:] == ["--stage-rows"]:
         stage_rows()
         route_rows()
