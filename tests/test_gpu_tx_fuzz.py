@@ -10,11 +10,20 @@ tests/tx_fuzz_runner.py holds what is asserted on every event: kernel_name() beh
 bits (k_tx_split16's output: the 1e-5 bar of tests/test_gpu_tx.py per 256 complex outputs, 1 LSB in int16), sync() == 0, no sticky status.
 
 Three tests, a slice of the cases each (tx_fuzz_cases.COUNTS; SELENITE_FUZZ_CASES=<n> scales them, 160 in all by default;
-SELENITE_FUZZ_ONLY=<index> runs one case of a slice).  A failure prints the whole case and the event index."""
+SELENITE_FUZZ_ONLY=<index> runs one case of a slice).  A failure prints the whole case and the event index.
+
+Two more tests, a slice each, for the instances on which a call can come in through three kinds of entry (tests/tx_entry_fuzz_cases.py):
+KEY with a keyed CW path (k_tx_cw: key calls in f32 and int16 through the host and the device entry, the sidetone stored or mixed, audio
+calls between them, retunes, checkpoints over a key call, a refused key call) and IN with an audio input stage (k_tx_in: frame calls
+through all five entries into k_tx_fused, k_tx_split16, k_tx_generic and k_tx_fm, with key and audio calls between them, VOX, retunes,
+checkpoints over a frame call, clear_in and a refused frame call).  tests/test_tx_entry_fuzz_cases.py asserts their coverage on the CPU;
+tx_fuzz_runner.EntryPair holds what is asserted: on top of the above, the stage's audio, the sidetone buffer, cw_state, in_state and
+fm_state on bits against tests/txin_oracle.py's TxInOracle.  The two environment variables work on them as on the three."""
 import os
 
 import pytest
 
+import tx_entry_fuzz_cases as ez
 import tx_fuzz_cases as fz
 import tx_fuzz_runner as fr
 
@@ -40,3 +49,20 @@ def test_generic_shapes_without_fm():
 
 def test_both_families_through_fm():
     run_slice("FM")
+
+
+def run_entry_slice(kind):
+    n = ez.scale_count(kind, os.environ.get("SELENITE_FUZZ_CASES"))
+    only = os.environ.get("SELENITE_FUZZ_ONLY")
+    for case in ez.cases(ez.SEED, n, kind):
+        if only is None or case["idx"] == int(only):
+            fr.run_entry_case(case)
+    print("tx entry fuzz %s: %d cases; worst k_tx_split16 per-block error so far %.3g of the block maximum (bar %g)" % (kind, n, fr.WORST[0], fr.TOL))
+
+
+def test_key_calls_between_audio_calls():
+    run_entry_slice("KEY")
+
+
+def test_frame_calls_between_key_and_audio_calls():
+    run_entry_slice("IN")

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import rxcommon as rc
+import tx_entry_fuzz_cases as ez
 import tx_fuzz_cases as fz
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -123,27 +124,37 @@ def _lds(s):
 def test_the_rule_agrees_with_the_fuzz_generators_restatement(prog):
     """every planned call of the committed cases, through `eval`: kernel family and flavour as walk() expects them, the instance's name as
     expected_kernel() does; the inputs are the case's own (taps classified by matrix_shape as selenite_tx_init does, the table where
-    selenite_tx_init builds it) and walk's phase_uniform in front of the call"""
+    selenite_tx_init builds it) and walk's phase_uniform in front of the call.  The cases of the entry fuzz (tests/tx_entry_fuzz_cases.py)
+    go the same way: a key call with key = 1 and k_tx_cw's LDS as cw_lds_bytes restates it, a frame call as the audio call it ends in;
+    phase_uniform behind a key call is walk's, which a key call clears as an FM call does."""
     flavours = {"off": 0, "perchan": 1, "table": 2, "periodic": 3, "zero_if": 0, "nco": 1}
-    families = {"generic": GENERIC, "fused": FUSED, "split16": SPLIT16, "fm": KFM}
+    families = {"generic": GENERIC, "fused": FUSED, "split16": SPLIT16, "fm": KFM, "cw": KCW}
     asked, want = [], []
-    for kind in fz.KINDS:
-        for case in fz.cases(fz.SEED, fz.COUNTS[kind], kind):
-            s = case["spec"]
-            classed = int(fz.matrix_shape(case))            # both tap classes or neither: what matrix_shape tells apart
-            steps = s["nco_steps"] if s["nco_steps"] is not None else [s["nco_step_all"]] * s["channels"]
-            table = int(classed and s["arith"] == rc.ARITH_SPLIT16)
-            lg, lf = _lds(s)
-            for _, r in fz.walk(case):
-                asked.append("%d %d %d %d %d %d %d %d %d %d %d %d 0 0 %d %d 0 %d %d 0" % (
-                    s["block"], s["interp"], s["ni_taps"], s["nh_taps"], classed, classed, s["arith"], r["mode"], int(bool(s["nco"])),
-                    int(len(set(steps)) == 1), int(bool(r["uniform"])), steps[0], table, r["bs"], lg, lf))
-                want.append((families[r["kernel"]], flavours[r["flavour"]], fz.expected_kernel(case, r["mode"]), case["kind"], case["idx"]))
+    for gen, kinds in ((fz, fz.KINDS), (ez, ez.KINDS)):
+        for kind in kinds:
+            for case in gen.cases(gen.SEED, gen.COUNTS[kind], kind):
+                s = case["spec"]
+                classed = int(fz.matrix_shape(case))            # both tap classes or neither: what matrix_shape tells apart
+                steps = s["nco_steps"] if s["nco_steps"] is not None else [s["nco_step_all"]] * s["channels"]
+                table = int(classed and s["arith"] == rc.ARITH_SPLIT16)
+                lg, lf = _lds(s)
+                cw = case.get("cw")
+                for i, r in gen.walk(case):
+                    key = int(r.get("entry") == "key")
+                    if key:                                      # (the setting of the call: a retune in front of it counts)
+                        ns = [ev["cw"] for ev in case["events"][:i] if ev["op"] == "set_cw"][-1:] or [cw]
+                        assert ns[0]["ns_taps"] == r["ns"]
+                    lc = ez.cw_lds_bytes(s["block"], s["interp"], s["ni_taps"], r["ns"]) if key else 0
+                    asked.append("%d %d %d %d %d %d %d %d %d %d %d %d 0 0 %d %d %d %d %d %d" % (
+                        s["block"], s["interp"], s["ni_taps"], s["nh_taps"], classed, classed, s["arith"], r["mode"], int(bool(s["nco"])),
+                        int(len(set(steps)) == 1), int(bool(r["uniform"])), steps[0], table, r["bs"], key, lg, lf, lc))
+                    name = fz.expected_kernel(case, r["mode"])      # (the instance's name: a key call does not change it)
+                    want.append((families[r["kernel"]], flavours[r["flavour"]], name, int(key or r["mode"] == fz.FM), case["kind"], case["idx"]))
     out = subprocess.run([prog, "eval"], input="\n".join(asked) + "\n", check=True, stdout=subprocess.PIPE, text=True).stdout.splitlines()
-    assert len(out) == len(want) > 400
+    assert len(out) == len(want) > 800
     seen = set()
-    for line, (kernel, flavour, name, kind, idx) in zip(out, want):
-        k, f, _, _, refused, got_name = line.split(" ", 5)
-        assert (int(k), int(f), int(refused), got_name) == (kernel, flavour, 0, name), (kind, idx, line)
+    for line, (kernel, flavour, name, clears, kind, idx) in zip(out, want):
+        k, f, _, got_clears, refused, got_name = line.split(" ", 5)
+        assert (int(k), int(f), int(got_clears), int(refused), got_name) == (kernel, flavour, clears, 0, name), (kind, idx, line)
         seen.add((kernel, flavour))
-    assert {(SPLIT16, 3), (SPLIT16, 2), (FUSED, 2), (FUSED, 1), (GENERIC, 1), (GENERIC, 0), (KFM, 1), (KFM, 0)} <= seen
+    assert {(SPLIT16, 3), (SPLIT16, 2), (FUSED, 2), (FUSED, 1), (GENERIC, 1), (GENERIC, 0), (KFM, 1), (KFM, 0), (KCW, 1), (KCW, 0)} <= seen
