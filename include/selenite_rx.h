@@ -29,6 +29,7 @@
  *   -> arm_sub_f32 / arm_add_f32 (USB / LSB)   [AM: arm_cmplx_mag_f32]
  *   -> arm_biquad_cascade_df1_f32 (CW narrow filter)
  *   -> [optional tap: Goertzel tone-detector bank (CTCSS, DTMF, selcall), selenite_rx_set_tones]
+ *   -> [optional tap: arm_power_f32 per DSP block -> Morse decoder (CW skimmer), selenite_rx_set_cwdec]
  *   -> [optional: arm_biquad_cascade_df1_f32 audio filter (notch, de-emphasis, EQ), selenite_rx_set_afilt]
  *   -> [optional: arm_lms_norm_f32 noise reduction / automatic notch, selenite_rx_set_nr]
  *   -> [optional: arm_power_f32 per DSP block -> level meter -> squelch decision, selenite_rx_set_meter]
@@ -483,6 +484,80 @@ typedef struct selenite_rx_tones_state_view {
     uint64_t *position;       /* ONE value: DSP blocks per channel since set_tones / reset */
 } selenite_rx_tones_state_view;
 
+/* ---- Morse decoder, a CW skimmer (a TAP on the un-scaled audio behind the demodulator and
+ * the CW filter, in front of the audio filter, NLMS, the level meter and the AGC; off by default) ------------------------------------------
+ * The stage is a tap, off by default, available in every mode and every `arith` mode.  It reads the un-scaled audio behind the
+ * demodulator and behind the CW filter (step 4).  That is the tone bank's position, in front of 4a / 4b / 4c / the AGC.  It changes none
+ * of the audio.  One tick is one DSP block of n = block / decim samples x.
+ * Every float operation is rounded to f32, with no contraction and denormals kept.  The division is correctly rounded.  These are the
+ * meter's rules.
+ * State per channel, with its value after set_cwdec / reset in brackets: peak, floor (f32; +0.0f); primed, key, flip, run (u32; 0);
+ * unit (u32, Q8 blocks; unit_init); code (u32; 1); word (u32; 0); count (u64; 0); text[ring] (u8; 0).
+ *   pw = arm_power_f32(x, n);  ms = pw / (float)n
+ *   raw = 0
+ *   if (ms <= FLT_MAX) {                                   (false for NaN: peak, floor stay, raw = 0)
+ *       if (!primed) { peak = ms; floor = ms; primed = 1; }
+ *       else {
+ *           r = ms > peak  ? peak_attack  : peak_decay;   d = ms - peak;   t = r * d;  peak  = peak  + t;
+ *           r = ms < floor ? floor_attack : floor_decay;  d = ms - floor;  t = r * d;  floor = floor + t;
+ *       }
+ *       span = peak - floor;  f = key ? off_frac : on_frac;  t = f * span;  thr = floor + t;
+ *       q = snr * floor;  active = peak > q && peak > min_power;
+ *       raw = active && ms > thr;
+ *   }
+ *   edge = 0
+ *   if (raw == key) { run = min(run + flip + 1, 65535); flip = 0; }
+ *   else { flip += 1;  if (flip >= debounce) { ended = run; key = raw; run = flip; flip = 0; edge = 1; } }
+ *   if (edge && key == 0) {                                (a mark of `ended` blocks is over)
+ *       m = ended << 8;  dah = m >= 2 * unit;              (unit as it stood before this update)
+ *       if (adapt) { g = dah ? m / 3 : m;
+ *                    if (g >= unit) unit += (g - unit) >> track; else unit -= (unit - g) >> track;
+ *                    unit = min(max(unit, unit_min), unit_max); }
+ *       code = (code == 0 || code >= 128) ? 0 : (code << 1) | dah;       (0: more than 7 elements)
+ *   }
+ *   if (key == 0) {
+ *       s = run << 8;
+ *       if (code != 1 && s >= 2 * unit) { emit(table[code]); code = 1; word = 1; }
+ *       if (word && s >= 5 * unit)      { emit(' ');         word = 0; }
+ *   }
+ *   emit(c):  text[count % ring] = c;  count += 1
+ * `table` is 256 bytes, copied, indexed by the element pattern behind a leading 1.  `.-` is 0b101.  Index 0 is the overflow character.
+ * The stage neither raises nor clears SELENITE_RX_NANINF.  One set of parameters and one table for all channels. */
+typedef struct selenite_rx_cwdec_config {
+    uint32_t struct_size;     /* = sizeof(selenite_rx_cwdec_config) (this struct's own growth path) */
+    float peak_attack;        /* the four follower rates: finite, in (0, 1] */
+    float peak_decay;
+    float floor_attack;
+    float floor_decay;
+    float on_frac;            /* 0 < off_frac <= on_frac < 1 */
+    float off_frac;
+    float snr;                /* finite, >= 1 */
+    float min_power;          /* finite, >= 0 */
+    uint32_t debounce;        /* 1 .. 255 */
+    uint32_t adapt;           /* 0 / 1 */
+    uint32_t track;           /* 0 .. 8 */
+    uint32_t unit_min;        /* Q8 blocks: 256 <= unit_min <= unit_init <= unit_max <= 8192 * 256 */
+    uint32_t unit_init;
+    uint32_t unit_max;
+    uint32_t ring;            /* a power of two, 16 .. 65536: characters kept per channel */
+    const uint8_t *table;     /* [256], copied; NULL selects the built-in table (selenite_rx_design_morse with unknown = '#') */
+} selenite_rx_cwdec_config;
+
+/* The stage's whole state.  NULL members are skipped. */
+typedef struct selenite_rx_cwdec_state_view {
+    float *peak;              /* [channels] */
+    float *floor;             /* [channels] */
+    uint32_t *primed;         /* [channels] 0 / 1 */
+    uint32_t *key;            /* [channels] 0 / 1: the debounced key */
+    uint32_t *flip;           /* [channels] consecutive blocks against `key` */
+    uint32_t *run;            /* [channels] blocks of the running mark or space, saturating at 65535 */
+    uint32_t *unit;           /* [channels] the dit length, Q8 blocks */
+    uint32_t *code;           /* [channels] the elements of the running character behind a leading 1; 0: overflow */
+    uint32_t *word;           /* [channels] 0 / 1: a character is out and its word space is not */
+    uint64_t *count;          /* [channels] characters emitted since set_cwdec / reset */
+    uint8_t *text;            /* [channels][ring] */
+} selenite_rx_cwdec_state_view;
+
 typedef struct selenite_rx_instance selenite_rx_instance;  /* opaque; state lives in HBM */
 
 /* ---- instance life cycle ------------------------------------------------------------- */
@@ -755,6 +830,29 @@ int selenite_rx_get_tones(selenite_rx_instance *S, uint32_t *tone, float *power,
 const uint32_t *selenite_rx_tones_tone_device(const selenite_rx_instance *S);
 const float *selenite_rx_tones_power_device(const selenite_rx_instance *S);
 
+/* Morse decoder (the law: selenite_rx_cwdec_config above).  f == NULL removes the stage and releases its buffers.  Puts the stage's state
+ * at its start.  Drains the instance's stream first.  SELENITE_RX_ARGUMENT_ERROR (a field outside its range as the struct states them, a
+ * wrong struct_size) leaves the instance as it was, a working stage included.  SELENITE_RX_DEVICE_ERROR is different: the old stage is
+ * released before the new rows are allocated, so a failed allocation leaves the instance with NO stage (as after f == NULL).
+ * selenite_rx_set_mode and every other setter leave it alone; selenite_rx_reset returns it to its state after set_cwdec and keeps the
+ * parameters and the table.  Every process entry point runs it once per call (f32 and int16 slots, device and host pointers, the timing
+ * calls, global phase 1, selenite_rx_global_process_f32_device -- not phase 2); the state rows of a channel chunk of a host-pointer call
+ * move with its first channel.  With the stage on, the fused kernels run with their own AGC off and the generic AGC kernel finishes the
+ * call, as with NLMS.  With the stage off no launch, byte, allocation or output of any call changes. */
+int selenite_rx_set_cwdec(selenite_rx_instance *S, const selenite_rx_cwdec_config *f);
+/* Host copies of the state.  Drain the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the stage is off. */
+int selenite_rx_get_cwdec_state(selenite_rx_instance *S, const selenite_rx_cwdec_state_view *dst);
+int selenite_rx_set_cwdec_state(selenite_rx_instance *S, const selenite_rx_cwdec_state_view *src);
+/* Host copies of what a reader wants: text [channels][ring], count, unit, key [channels].  Character i of a channel (i < count, i >=
+ * count - ring) is text[i % ring].  NULL arguments are skipped.  Drains the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the
+ * stage is off. */
+int selenite_rx_get_cwdec(selenite_rx_instance *S, uint8_t *text, uint64_t *count, uint32_t *unit, uint32_t *key);
+/* The rows on the device, readable on the instance's stream behind a call; NULL while the stage is off; valid until the next
+ * selenite_rx_set_cwdec or selenite_rx_free. */
+const uint8_t *selenite_rx_cwdec_text_device(const selenite_rx_instance *S);
+const uint64_t *selenite_rx_cwdec_count_device(const selenite_rx_instance *S);
+const uint32_t *selenite_rx_cwdec_unit_device(const selenite_rx_instance *S);
+
 void *selenite_rx_device_alloc(size_t bytes);          /* hipMalloc; NULL on failure */
 void  selenite_rx_device_free(void *dptr);
 int   selenite_rx_memcpy_h2d(void *dptr, const void *hptr, size_t bytes);
@@ -875,6 +973,11 @@ int selenite_rx_design_deemphasis(float coeffs[5], double tau_samples);
 int selenite_rx_design_tones(float *coeffs, const double *freq, uint32_t n_tones);
 /* The 50 standard CTCSS frequencies in Hz, ascending, 67.0 .. 254.1; returns 50. */
 uint32_t selenite_rx_ctcss_hz(double hz[50]);
+
+/* The Morse decoder's table: index = the element pattern behind a leading 1, dit 0, dah 1, first element highest (`.-` is 0b101 = 5).
+ * A-Z, 0-9, . (.-.-.-) , (--..--) ? (..--..) / (-..-.) = (-...-) + (.-.-.) - (-....-) @ (.--.-.); every other index, 0 (the overflow
+ * character) included, is `unknown`.  Host only. */
+int selenite_rx_design_morse(uint8_t table[256], uint8_t unknown);
 
 int selenite_rx_abi_version(void);
 

@@ -160,6 +160,29 @@ extern "C" uint32_t selenite_rx_ctcss_hz(double hz[50])
     return 50u;
 }
 
+// the Morse decoder's table (rx_cwdec.hip): index = the elements behind a leading 1, dit 0, dah 1
+extern "C" int selenite_rx_design_morse(uint8_t table[256], uint8_t unknown)
+{
+    static const struct { char c; const char *pattern; } kMorse[] = {
+        { 'A', ".-" },    { 'B', "-..." },  { 'C', "-.-." },  { 'D', "-.." },   { 'E', "." },     { 'F', "..-." },  { 'G', "--." },
+        { 'H', "...." },  { 'I', ".." },    { 'J', ".---" },  { 'K', "-.-" },   { 'L', ".-.." },  { 'M', "--" },    { 'N', "-." },
+        { 'O', "---" },   { 'P', ".--." },  { 'Q', "--.-" },  { 'R', ".-." },   { 'S', "..." },   { 'T', "-" },     { 'U', "..-" },
+        { 'V', "...-" },  { 'W', ".--" },   { 'X', "-..-" },  { 'Y', "-.--" },  { 'Z', "--.." },
+        { '0', "-----" }, { '1', ".----" }, { '2', "..---" }, { '3', "...--" }, { '4', "....-" }, { '5', "....." }, { '6', "-...." },
+        { '7', "--..." }, { '8', "---.." }, { '9', "----." },
+        { '.', ".-.-.-" }, { ',', "--..--" }, { '?', "..--.." }, { '/', "-..-." }, { '=', "-...-" }, { '+', ".-.-." }, { '-', "-....-" },
+        { '@', ".--.-." },
+    };
+    if (!table) return SELENITE_RX_ARGUMENT_ERROR;
+    for (int i = 0; i < 256; ++i) table[i] = unknown;
+    for (const auto &m : kMorse) {
+        uint32_t code = 1u;
+        for (const char *p = m.pattern; *p; ++p) code = (code << 1) | (*p == '-' ? 1u : 0u);
+        table[code] = (uint8_t)m.c;
+    }
+    return SELENITE_RX_SUCCESS;
+}
+
 // include/selenite_tx.h: the phase increment per output sample of a tone of `hz` at the output rate `fs_out`, for
 // selenite_tx_fm_config::tone_step (and nco_step): round(hz / fs_out * 2^32) in double, rounded once, modulo 2^32 (a negative
 // frequency is its two's complement); 0 for arguments that are not finite or a rate that is not positive

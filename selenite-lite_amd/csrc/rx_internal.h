@@ -375,6 +375,38 @@ struct __attribute__((visibility("hidden"))) TonesStage {
     TonesParams params(ChanRange r, const RxParams &p, uint32_t blocks_before) const;
 };
 
+// ---- Morse decoder (rx_cwdec.hip): arm_power_f32 per DSP block of the un-scaled audio -> peak / floor followers -> debounced key ->
+// element timing -> text, a tap at the tone bank's place ----
+struct CwdecParams {
+    uint32_t channels;     // channels of this launch (a ChanRange: the state rows and `text` are offset to it)
+    uint32_t n;            // audio samples of a DSP block: block / decim
+    uint32_t nblk;         // DSP blocks per channel in this launch
+    uint32_t stride;       // audio samples between consecutive channels (RxParams::out_stride)
+    float peak_attack, peak_decay, floor_attack, floor_decay, on_frac, off_frac, snr, min_power;
+    uint32_t debounce, adapt, track, unit_min, unit_max;
+    uint32_t ring;         // a power of two
+    const uint8_t *table;  // [256]
+    float *peak, *floor;   // [C] each
+    uint32_t *primed, *key, *flip, *run, *unit, *code, *word;      // [C] each
+    uint64_t *count;       // [C]
+    uint8_t *text;         // [C][ring]
+};
+hipError_t launch_cwdec(const CwdecParams &q, const float *audio, hipStream_t st);
+// the stage's part of the instance (selenite_rx_set_cwdec): on = false: no stage, no buffers
+struct __attribute__((visibility("hidden"))) CwdecStage {
+    bool on = false;
+    float peak_attack = 0.0f, peak_decay = 0.0f, floor_attack = 0.0f, floor_decay = 0.0f, on_frac = 0.0f, off_frac = 0.0f, snr = 0.0f, min_power = 0.0f;
+    uint32_t debounce = 0, adapt = 0, track = 0, unit_min = 0, unit_init = 0, unit_max = 0, ring = 0;
+    uint8_t *d_table = nullptr;                             // [256]
+    float *d_peak = nullptr, *d_floor = nullptr;            // [channels] each
+    uint32_t *d_primed = nullptr, *d_key = nullptr, *d_flip = nullptr, *d_run = nullptr, *d_unit = nullptr, *d_code = nullptr, *d_word = nullptr;
+    uint64_t *d_count = nullptr;                            // [channels]
+    uint8_t *d_text = nullptr;                              // [channels][ring]
+    void release();                                         // frees the buffers: no stage
+    int init_state(selenite_rx_instance *S);                // the state set_cwdec leaves
+    CwdecParams params(ChanRange r, const RxParams &p) const;   // the stage's view of a launch: the channels and the audio geometry of `p`
+};
+
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
     SelPlan sel;                  // what select() reads: the shape (kind 0 = none), dense or not, which operands exist (rx_select.h)
@@ -469,6 +501,7 @@ struct selenite_rx_instance {
     int no_periodic_lo = 0;            // SELENITE_RX_NO_PERIODIC_LO=1: never keep a periodic shared LO in registers
     int force_generic = 0;             // SELENITE_RX_FORCE_GENERIC=1 (tests cross-check both paths)
     srx::TonesStage tones;             // tone-detector bank, a tap behind the demodulator / CW filter, in front of the audio filter (rx_tones.hip)
+    srx::CwdecStage cwdec;             // Morse decoder, a tap at the tone bank's place (rx_cwdec.hip)
     srx::AfiltStage afilt;             // audio biquad filter, behind the demodulator / CW filter, in front of NLMS (rx_afilt.hip)
     srx::NrStage nr;                   // NLMS noise reduction / automatic notch, in front of the AGC (rx_nlms.hip)
     srx::MeterStage meter;             // signal-level meter and squelch, between NLMS and the AGC; its gate behind the AGC (rx_meter.hip)

@@ -146,6 +146,27 @@ class TonesStateView(C.Structure):
 
 TONES_MAX, TONE_NONE = 64, 0xFFFFFFFF
 
+u8p = C.POINTER(C.c_uint8)
+
+
+class CwdecConfig(C.Structure):
+    """struct selenite_rx_cwdec_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("peak_attack", C.c_float), ("peak_decay", C.c_float), ("floor_attack", C.c_float),
+                ("floor_decay", C.c_float), ("on_frac", C.c_float), ("off_frac", C.c_float), ("snr", C.c_float), ("min_power", C.c_float),
+                ("debounce", C.c_uint32), ("adapt", C.c_uint32), ("track", C.c_uint32), ("unit_min", C.c_uint32), ("unit_init", C.c_uint32),
+                ("unit_max", C.c_uint32), ("ring", C.c_uint32), ("table", u8p)]
+
+
+class CwdecStateView(C.Structure):
+    """struct selenite_rx_cwdec_state_view."""
+    _fields_ = [("peak", f32p), ("floor", f32p), ("primed", u32p), ("key", u32p), ("flip", u32p), ("run", u32p), ("unit", u32p),
+                ("code", u32p), ("word", u32p), ("count", u64p), ("text", u8p)]
+
+
+# the documented defaults of Rx.set_cwdec (10 - 40 WPM at DSP blocks of about 5 ms)
+CWDEC_DEFAULTS = dict(peak_attack=0.5, peak_decay=0.002, floor_attack=0.25, floor_decay=0.002, on_frac=0.4, off_frac=0.25, snr=4.0,
+                      min_power=1e-8, debounce=2, adapt=1, track=2, unit_min=2 * 256, unit_init=10 * 256, unit_max=64 * 256, ring=256)
+
 # every symbol include/selenite_rx.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "selenite_rx_init", "selenite_rx_free", "selenite_rx_set_mode", "selenite_rx_status",
@@ -175,6 +196,8 @@ ABI_SYMBOLS = [
     "selenite_rx_design_biquad", "selenite_rx_design_deemphasis",
     "selenite_rx_set_tones", "selenite_rx_get_tones_state", "selenite_rx_set_tones_state", "selenite_rx_get_tones",
     "selenite_rx_tones_tone_device", "selenite_rx_tones_power_device", "selenite_rx_design_tones", "selenite_rx_ctcss_hz",
+    "selenite_rx_set_cwdec", "selenite_rx_get_cwdec_state", "selenite_rx_set_cwdec_state", "selenite_rx_get_cwdec",
+    "selenite_rx_cwdec_text_device", "selenite_rx_cwdec_count_device", "selenite_rx_cwdec_unit_device", "selenite_rx_design_morse",
 ]
 
 class TxConfig(C.Structure):
@@ -439,6 +462,15 @@ def lib():
             L.selenite_rx_design_tones.argtypes = [f32p, C.POINTER(C.c_double), C.c_uint32]
             L.selenite_rx_ctcss_hz.argtypes = [C.POINTER(C.c_double)]
             L.selenite_rx_ctcss_hz.restype = C.c_uint32
+        if hasattr(L, "selenite_rx_set_cwdec"):             # (an older build named by SELENITE_RX_LIB lacks the Morse decoder)
+            L.selenite_rx_set_cwdec.argtypes = [vp, C.POINTER(CwdecConfig)]
+            L.selenite_rx_get_cwdec_state.argtypes = [vp, C.POINTER(CwdecStateView)]
+            L.selenite_rx_set_cwdec_state.argtypes = [vp, C.POINTER(CwdecStateView)]
+            L.selenite_rx_get_cwdec.argtypes = [vp, u8p, u64p, u32p, u32p]
+            for n in ("text", "count", "unit"):
+                getattr(L, "selenite_rx_cwdec_%s_device" % n).argtypes = [vp]
+                getattr(L, "selenite_rx_cwdec_%s_device" % n).restype = vp
+            L.selenite_rx_design_morse.argtypes = [u8p, C.c_uint8]
         if hasattr(L, "selenite_tx_set_fm"):                # (an older build named by SELENITE_RX_LIB lacks the FM transmit mode)
             L.selenite_tx_set_fm.argtypes = [vp, C.POINTER(TxFmConfig)]
             L.selenite_tx_get_fm_state.argtypes = [vp, C.POINTER(TxFmStateView)]
@@ -559,6 +591,56 @@ def design_tones(freq):
     if rc:
         raise ValueError("selenite_rx_design_tones: %d" % rc)
     return c
+
+
+def morse_table(unknown="#"):
+    """the Morse decoder's built-in table (selenite_rx_design_morse): uint8 [256], index = the element pattern behind a leading 1 (dit 0,
+    dah 1; `.-` is 0b101); every index without a character, 0 (overflow) included, is `unknown`"""
+    t = np.zeros(256, np.uint8)
+    rc = lib().selenite_rx_design_morse(t.ctypes.data_as(u8p), ord(unknown) if isinstance(unknown, str) else int(unknown))
+    if rc:
+        raise ValueError("selenite_rx_design_morse: %d" % rc)
+    return t
+
+
+def ring_text(ring, count):
+    """the last min(count, len(ring)) characters of one channel's ring in order, as str (character i lies at ring[i % len(ring)])"""
+    ring = np.asarray(ring, np.uint8)
+    n = len(ring)
+    if count <= n:
+        return ring[:count].tobytes().decode("latin-1")
+    at = count % n
+    return (ring[at:].tobytes() + ring[:at].tobytes()).decode("latin-1")
+
+
+def morse_key(text, unit_samples, table=None):
+    """key bytes (uint8 0 / 1 per sample) of `text` for Tx.process_key and the tests: a dit is unit_samples samples down, a dah three
+    times that; one unit up between the elements of a character, three between characters, seven for a blank.  Starts with the first
+    element and ends with the last one: the caller adds the silence around it.  Characters are looked up in `table` (morse_table())."""
+    t = morse_table() if table is None else np.asarray(table, np.uint8)
+    code_of = {}
+    for code in range(2, 256):
+        code_of.setdefault(int(t[code]), code)
+    unit_samples = int(unit_samples)
+    if unit_samples < 1:
+        raise ValueError("morse_key: unit_samples < 1")
+    units, gap = [], 0                           # (down?, units) runs
+    for ch in text.upper():
+        if ch == " ":
+            gap = 7 if units else 0
+            continue
+        code = code_of.get(ord(ch)) if ord(ch) != int(t[0]) else None
+        if code is None:
+            raise ValueError("morse_key: no pattern for %r" % ch)
+        if gap or units:
+            units.append((0, gap or 3))
+        gap = 0
+        els = [(code >> b) & 1 for b in range(code.bit_length() - 2, -1, -1)]
+        for i, dah in enumerate(els):
+            if i:
+                units.append((0, 1))
+            units.append((1, 3 if dah else 1))
+    return np.concatenate([np.full(u * unit_samples, d, np.uint8) for d, u in units]) if units else np.zeros(0, np.uint8)
 
 
 def ctcss_hz():
@@ -1359,6 +1441,103 @@ class Rx:
     def tones_power_device(self):
         """device address of the power rows (None while the stage is off)"""
         return self.L.selenite_rx_tones_power_device(self.h)
+
+    # -- Morse decoder (selenite_rx_set_cwdec) ----------------------------------------------------------
+    CWDEC_TYPES = dict(peak=np.float32, floor=np.float32, primed=np.uint32, key=np.uint32, flip=np.uint32, run=np.uint32, unit=np.uint32,
+                       code=np.uint32, word=np.uint32, count=np.uint64, text=np.uint8)
+    CWDEC_PTRS = dict(peak=f32p, floor=f32p, primed=u32p, key=u32p, flip=u32p, run=u32p, unit=u32p, code=u32p, word=u32p, count=u64p, text=u8p)
+
+    def set_cwdec(self, on=True, table=None, **par):
+        """Put the Morse decoder on the un-scaled audio of every channel (a tap at the tone bank's place: it changes no audio), or remove
+        it (set_cwdec(None)).  par: the fields of selenite_rx_cwdec_config; the defaults are CWDEC_DEFAULTS: peak_attack 0.5, peak_decay
+        0.002, floor_attack 0.25, floor_decay 0.002, on_frac 0.4, off_frac 0.25, snr 4, min_power 1e-8, debounce 2, adapt 1, track 2,
+        unit_min 2 * 256, unit_init 10 * 256, unit_max 64 * 256 (Q8 DSP blocks), ring 256.  table: uint8 [256] (None: morse_table()).
+        Puts the stage's state at its start.  Raises RxError on a bad field; the instance is then left as it was."""
+        old, self._cwdec = getattr(self, "_cwdec", None), None
+        if on is None or on is False:
+            rc, new = self.L.selenite_rx_set_cwdec(self.h, None), None
+        else:
+            unknown = set(par) - set(CWDEC_DEFAULTS)
+            if unknown:
+                self._cwdec = old
+                raise TypeError("set_cwdec: unknown fields %s" % sorted(unknown))
+            p = dict(CWDEC_DEFAULTS, **par)
+            g = CwdecConfig()
+            g.struct_size = C.sizeof(CwdecConfig)
+            for k, v in p.items():
+                setattr(g, k, float(v) if isinstance(CWDEC_DEFAULTS[k], float) else int(v))
+            t = None
+            if table is not None:
+                t = np.ascontiguousarray(table, np.uint8)
+                if t.shape != (256,):
+                    self._cwdec = old
+                    raise RxError(ARGUMENT_ERROR, "set_cwdec: table is not [256]")
+                g.table = t.ctypes.data_as(u8p)
+            rc, new = self.L.selenite_rx_set_cwdec(self.h, C.byref(g)), int(p["ring"])
+        if rc == ARGUMENT_ERROR:
+            self._cwdec = old
+        if rc:
+            raise RxError(rc, self.L.selenite_rx_error_string(None).decode() if rc == ARGUMENT_ERROR else self.error())
+        self._cwdec = new
+
+    def _cwdec_shapes(self):
+        if getattr(self, "_cwdec", None) is None:
+            raise RxError(ARGUMENT_ERROR, "the Morse decoder is off")
+        ch = self.cfg.channels
+        return {k: ((ch, self._cwdec) if k == "text" else (ch,)) for k in self.CWDEC_TYPES}
+
+    def cwdec_state(self):
+        """dict(peak, floor f32; primed, key, flip, run, unit, code, word u32; count u64, each [channels]; text u8 [channels][ring]); drains
+        the stream"""
+        a = {k: np.zeros(sh, self.CWDEC_TYPES[k]) for k, sh in self._cwdec_shapes().items()}
+        v = CwdecStateView(*[a[k].ctypes.data_as(self.CWDEC_PTRS[k]) for k in self.CWDEC_TYPES])
+        rc = self.L.selenite_rx_get_cwdec_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_cwdec_state")
+        return a
+
+    def set_cwdec_state(self, d):
+        sh = self._cwdec_shapes()
+        a = {k: np.ascontiguousarray(d[k], self.CWDEC_TYPES[k]) for k in d}
+        for k in a:
+            assert a[k].shape == sh[k], (k, a[k].shape, sh[k])
+        v = CwdecStateView(*[a[k].ctypes.data_as(self.CWDEC_PTRS[k]) if k in a else None for k in self.CWDEC_TYPES])
+        rc = self.L.selenite_rx_set_cwdec_state(self.h, C.byref(v))
+        if rc:
+            raise RxError(rc, "selenite_rx_set_cwdec_state")
+
+    def cwdec(self):
+        """(text u8 [channels][ring], count u64, unit u32, key u32 [channels]): selenite_rx_get_cwdec; drains the stream"""
+        sh = self._cwdec_shapes()
+        text, count = np.zeros(sh["text"], np.uint8), np.zeros(sh["count"], np.uint64)
+        unit, key = np.zeros(sh["unit"], np.uint32), np.zeros(sh["key"], np.uint32)
+        rc = self.L.selenite_rx_get_cwdec(self.h, text.ctypes.data_as(u8p), count.ctypes.data_as(u64p), unit.ctypes.data_as(u32p),
+                                          key.ctypes.data_as(u32p))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_cwdec")
+        return text, count, unit, key
+
+    def cw_text(self, channel=None):
+        """the last min(count, ring) characters of a channel in order, as str; channel=None: a list for all channels.  Drains the stream."""
+        text, count, _, _ = self.cwdec()
+        out = [ring_text(text[c], int(count[c])) for c in (range(self.cfg.channels) if channel is None else [channel])]
+        return out if channel is None else out[0]
+
+    def cw_unit(self):
+        """the dit length of every channel in DSP blocks (unit / 256), float64 [channels]; drains the stream"""
+        return self.cwdec()[2].astype(np.float64) / 256.0
+
+    def cwdec_text_device(self):
+        """device address of the rings, u8 [channels][ring] (None while the stage is off)"""
+        return self.L.selenite_rx_cwdec_text_device(self.h)
+
+    def cwdec_count_device(self):
+        """device address of the count row, u64 [channels] (None while the stage is off)"""
+        return self.L.selenite_rx_cwdec_count_device(self.h)
+
+    def cwdec_unit_device(self):
+        """device address of the unit row, u32 [channels] (None while the stage is off)"""
+        return self.L.selenite_rx_cwdec_unit_device(self.h)
 
     def close(self):
         if self.h:
