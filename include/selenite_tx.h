@@ -116,5 +116,7 @@ int  selenite_tx_time_process_device(selenite_tx_instance *S, const float *dSrcA
 #include "selenite_tx_cw.h"
 /* the audio input stage (slot-rate L/R frames in: pick, mic gain, decimator, VOX; then the chain): selenite_tx_set_in and what goes with it */
 #include "selenite_tx_in.h"
+/* the keyer stage (iambic paddles, straight key and a Morse text memory in, key states out; then the keyed CW path): selenite_tx_set_keyer and what goes with it */
+#include "selenite_tx_keyer.h"
 
 #endif /* SELENITE_TX_H */

@@ -209,3 +209,31 @@ extern "C" int selenite_tx_design_keyshape(uint32_t ns_taps, float *coeffs)
     for (uint32_t k = 0; k < ns_taps; ++k) coeffs[k] = (float)(w[k] / sum);
     return SELENITE_RX_SUCCESS;
 }
+
+// include/selenite_tx_keyer.h: character -> element pattern, the inverse of selenite_rx_design_morse's table (NULL: the built-in one).
+// The smallest pattern >= 2 of a character wins; the filler table[0] has none; a lower-case letter takes its upper-case letter's; the
+// blank is 1 (the keyer's word blank); every other byte is 0 (the keyer skips and counts it).
+extern "C" int selenite_tx_design_morse_codes(uint8_t codes[256], const uint8_t table[256])
+{
+    if (!codes) return SELENITE_RX_ARGUMENT_ERROR;
+    uint8_t own[256];
+    if (!table) {
+        (void)selenite_rx_design_morse(own, (uint8_t)'#');
+        table = own;
+    }
+    for (int i = 0; i < 256; ++i) codes[i] = 0;
+    for (int code = 255; code >= 2; --code)
+        if (table[code] != table[0]) codes[table[code]] = (uint8_t)code;
+    for (int ch = 'a'; ch <= 'z'; ++ch)
+        if (codes[ch] == 0) codes[ch] = codes[ch - 'a' + 'A'];
+    codes[(uint8_t)' '] = 1;
+    return SELENITE_RX_SUCCESS;
+}
+
+// include/selenite_tx_keyer.h: the dit length in audio samples at `wpm` words per minute (PARIS: 50 units a word, 1.2 s / wpm a unit)
+extern "C" uint32_t selenite_tx_keyer_unit(double wpm, double fs_audio)
+{
+    if (!std::isfinite(wpm) || !std::isfinite(fs_audio) || !(wpm > 0.0) || !(fs_audio > 0.0)) return 0u;
+    const double u = std::round(1.2 * fs_audio / wpm);
+    return u < 1.0 ? 1u : (u > 4294967295.0 ? 4294967295u : (uint32_t)u);
+}

@@ -90,7 +90,7 @@ static int reset_state(selenite_tx_instance *S)
     if (nh1) HIPCHK(S, hipMemsetAsync(S->d_fir_state, 0, C * 2 * nh1 * sizeof(float), S->stream));
     if (p1) HIPCHK(S, hipMemsetAsync(S->d_int_state, 0, C * 2 * p1 * sizeof(float), S->stream));
     HIPCHK(S, hipMemsetAsync(S->d_phase, 0, C * sizeof(uint32_t), S->stream));
-    if (tx_fm_reset(S) || tx_cw_reset(S) || tx_in_reset(S)) return S->status;
+    if (tx_fm_reset(S) || tx_cw_reset(S) || tx_in_reset(S) || tx_keyer_reset(S)) return S->status;
     if (int rc = fill_rows(S, S->d_gain, C, &g.alc_gain_init)) return rc;      // (drains the stream)
     S->phase_host = 0;
     S->phase_uniform = S->sel.steps_same;
@@ -184,7 +184,7 @@ extern "C" int selenite_tx_init(selenite_tx_instance **out, const selenite_tx_co
 extern "C" void selenite_tx_free(selenite_tx_instance *S)
 {
     if (!S) return;
-    tx_fm_free(S); tx_cw_free(S); tx_in_free(S);
+    tx_fm_free(S); tx_cw_free(S); tx_in_free(S); tx_keyer_free(S);
     dev_free(S->d_ic, S->d_hc, S->d_dc, S->d_sintab, S->d_step, S->d_phase, S->d_fir_state, S->d_int_state, S->d_gain, S->d_io_in, S->d_io_out,
              S->d_lo, S->d_ttab16);
     if (S->own_stream) (void)hipStreamDestroy(S->own_stream);

@@ -345,6 +345,10 @@ static int process_key_host(selenite_tx_instance *S, const uint8_t *key, void *d
                        [&] { return run_key(S, static_cast<const uint8_t *>(S->d_io_in), S->d_io_out, side ? W.d_io_side : nullptr, q15, bs); });
 }
 
+// the two halves of a key call, for the keyer stage (tx_keyer.hip), which runs them on the bytes it generates
+int tx_key_call_ok(selenite_tx_instance *S, const void *key, const void *dst, uint32_t bs, const char *who) { return key_call_ok(S, key, dst, bs, who); }
+int tx_run_key(selenite_tx_instance *S, const uint8_t *key, void *dst, void *side, bool q15, uint32_t bs) { return run_key(S, key, dst, side, q15, bs); }
+
 static int cw_state_copy(selenite_tx_instance *S, const selenite_tx_cw_state_view *v, bool to_host)
 {
     if (!S || !v || !S->cw.set) return SELENITE_RX_ARGUMENT_ERROR;

@@ -1,6 +1,6 @@
 // tx_host.h -- what the host-side translation units of the TX direction share: the instance, error reporting (the generic helpers are
 // rx_host.h's, templates over the instance), the two call shapes every entry point has (host-pointer staging; timing is rx_host.h's
-// timed_loop), and the interfaces between tx_api.hip (instance, chain, run) and the stages' own files (tx_fm.hip, tx_cw.hip, tx_in.hip).
+// timed_loop), and the interfaces between tx_api.hip (instance, chain, run) and the stages' own files (tx_fm.hip, tx_cw.hip, tx_in.hip, tx_keyer.hip).
 // Host code only; not part of the C-ABI.
 #pragma once
 #include <initializer_list>
@@ -54,6 +54,14 @@ struct selenite_tx_instance {
         void *d_audio = nullptr;  // the stage's output of the last frame call: what run() then reads
         size_t audio_bytes = 0;
     } in;
+    struct Keyer {                // the keyer stage (selenite_tx_set_keyer, tx_keyer.hip); d_state holds the eleven state rows, [word][channels]
+        bool set = false;
+        srx::TxKeyerParams p{};
+        uint32_t *d_unit = nullptr, *d_state = nullptr;
+        uint8_t *d_codes = nullptr, *d_text = nullptr;
+        void *d_key = nullptr;    // the stage's output of the last paddle call: what the keyed launch then reads
+        size_t key_bytes = 0;
+    } keyer;
     hipStream_t stream = nullptr, own_stream = nullptr;
     int status = 0;
     std::string err;
@@ -105,6 +113,11 @@ void tx_cw_free(selenite_tx_instance *S);
 int tx_cw_reset(selenite_tx_instance *S);
 void tx_in_free(selenite_tx_instance *S);
 int tx_in_reset(selenite_tx_instance *S);
+void tx_keyer_free(selenite_tx_instance *S);
+int tx_keyer_reset(selenite_tx_instance *S);
+// tx_cw.hip, for the keyer: a key call's refusals (0: none) and its launch on device pointers
+int tx_key_call_ok(selenite_tx_instance *S, const void *key, const void *dst, uint32_t block_size, const char *who);
+int tx_run_key(selenite_tx_instance *S, const uint8_t *key, void *dst, void *side, bool q15, uint32_t block_size);
 
 }  // namespace srx
 #pragma GCC visibility pop

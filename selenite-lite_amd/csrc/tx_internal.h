@@ -1,5 +1,5 @@
 // tx_internal.h -- kernel parameter blocks and launch interfaces of the TX kernels' files (tx_generic.hip, tx_fused.hip, tx_fm.hip,
-// tx_cw.hip, tx_in.hip), as tx_api.hip and the stages' host sides call them.
+// tx_cw.hip, tx_in.hip, tx_keyer.hip), as tx_api.hip and the stages' host sides call them.
 // Not part of the C-ABI (include/selenite_tx.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -81,5 +81,17 @@ struct TxInParams {
 uint32_t tx_in_tile(const TxInParams &q);          // outputs of a tile: a whole number of DSP blocks
 size_t tx_in_lds_bytes(const TxInParams &q);       // the sum in 64 bits
 hipError_t launch_tx_in(const TxInParams &q, const void *frames, bool in_q15, void *audio, bool out_q15, hipStream_t st);
+
+// tx_keyer.hip: the keyer stage (selenite_tx_set_keyer, include/selenite_tx_keyer.h).  k_tx_keyer: paddle bytes (or NULL) and the text
+// memory in, key bytes out, one single-wave workgroup per channel; integers only, no arith mode
+struct TxKeyerParams {
+    uint32_t channels, block_size;                 // the call length in AUDIO samples
+    uint32_t mode, ring;
+    const uint32_t *unit;                          // [C]
+    const uint8_t *codes;                          // [256]
+    const uint8_t *text;                           // [C][ring]
+    uint32_t *state;                               // [11][C]: phase, left, last, dit_mem, dah_mem, squeeze, code, tgap, tail, head, skipped
+};
+hipError_t launch_tx_keyer(const TxKeyerParams &q, const uint8_t *paddles, uint8_t *key, hipStream_t st);
 
 }  // namespace srx

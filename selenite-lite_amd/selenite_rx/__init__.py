@@ -27,6 +27,8 @@ WINDOW_HANN, WINDOW_BLACKMAN_HARRIS = 0, 1                     # selenite_rx_des
 SQ_ABOVE, SQ_BELOW = 0, 1                                      # selenite_rx_set_meter: the squelch's sense
 IN_MONO, IN_LEFT, IN_RIGHT, IN_MIX = 0, 1, 2, 3                # selenite_tx_set_in: which words of a frame make the audio
 IN_F32, IN_Q15, IN_Q15_F32 = 0, 1, 2                           # the frame entries: f32 -> f32 I/Q, int16 -> int16 I/Q, int16 -> f32 I/Q
+KEYER_STRAIGHT, KEYER_IAMBIC_A, KEYER_IAMBIC_B = 0, 1, 2       # selenite_tx_set_keyer: the mode
+PADDLE_DIT, PADDLE_DAH, PADDLE_KEY = 1, 2, 4                   # the paddle byte's bits
 
 f32p = C.POINTER(C.c_float)
 u32p = C.POINTER(C.c_uint32)
@@ -281,6 +283,29 @@ TXIN_ABI_SYMBOLS = [
     "selenite_tx_in_vox_device", "selenite_tx_in_audio_device", "selenite_tx_time_in_stage_device",
 ]
 
+class TxKeyerConfig(C.Structure):
+    """struct selenite_tx_keyer_config (include/selenite_tx_keyer.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_uint32), ("unit_all", C.c_uint32), ("unit", u32p), ("ring", C.c_uint32),
+                ("codes", C.POINTER(C.c_uint8)), ("reserved", C.c_uint32)]
+
+
+KEYER_STATE_WORDS = ("phase", "left", "last", "dit_mem", "dah_mem", "squeeze", "code", "tgap", "tail", "head", "skipped")
+
+
+class TxKeyerStateView(C.Structure):
+    """struct selenite_tx_keyer_state_view."""
+    _fields_ = [(k, u32p) for k in KEYER_STATE_WORDS] + [("text", C.POINTER(C.c_uint8))]
+
+
+# every symbol include/selenite_tx_keyer.h declares (the keyer stage; selenite_tx.h includes it)
+TXKEYER_ABI_SYMBOLS = [
+    "selenite_tx_set_keyer", "selenite_tx_keyer_send", "selenite_tx_keyer_pending",
+    "selenite_tx_process_paddles_f32_device", "selenite_tx_process_paddles_q15_device", "selenite_tx_process_paddles_f32",
+    "selenite_tx_process_paddles_q15", "selenite_tx_keyer_run_device", "selenite_tx_keyer_key_device",
+    "selenite_tx_get_keyer_state", "selenite_tx_set_keyer_state", "selenite_tx_time_keyer_stage_device",
+    "selenite_tx_design_morse_codes", "selenite_tx_keyer_unit",
+]
+
 # every symbol include/selenite_ring.h declares
 RING_ABI_SYMBOLS = [
     "selenite_ring_init", "selenite_ring_free", "selenite_ring_status", "selenite_ring_error_string",
@@ -498,6 +523,21 @@ def lib():
             L.selenite_tx_in_audio_device.argtypes = [vp]
             L.selenite_tx_in_audio_device.restype = vp
             L.selenite_tx_time_in_stage_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        if hasattr(L, "selenite_tx_set_keyer"):             # (an older build named by SELENITE_RX_LIB lacks the keyer stage)
+            L.selenite_tx_set_keyer.argtypes = [vp, C.POINTER(TxKeyerConfig)]
+            L.selenite_tx_keyer_send.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32]
+            L.selenite_tx_keyer_pending.argtypes = [vp, u32p]
+            for n in ("f32_device", "q15_device", "f32", "q15"):
+                getattr(L, "selenite_tx_process_paddles_" + n).argtypes = [vp, vp, vp, vp, C.c_uint32]
+            L.selenite_tx_keyer_run_device.argtypes = [vp, vp, vp, C.c_uint32]
+            L.selenite_tx_keyer_key_device.argtypes = [vp]
+            L.selenite_tx_keyer_key_device.restype = vp
+            L.selenite_tx_get_keyer_state.argtypes = [vp, C.POINTER(TxKeyerStateView)]
+            L.selenite_tx_set_keyer_state.argtypes = [vp, C.POINTER(TxKeyerStateView)]
+            L.selenite_tx_time_keyer_stage_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+            L.selenite_tx_design_morse_codes.argtypes = [u8p, u8p]
+            L.selenite_tx_keyer_unit.argtypes = [C.c_double, C.c_double]
+            L.selenite_tx_keyer_unit.restype = C.c_uint32
         L.selenite_rx_design_lowpass.argtypes = [f32p, C.c_uint32, C.c_double]
         L.selenite_rx_design_hilbert.argtypes = [f32p, f32p, C.c_uint32]
         L.selenite_rx_design_bandpass.argtypes = [f32p, C.c_uint32, C.c_double, C.c_double]
@@ -641,6 +681,24 @@ def morse_key(text, unit_samples, table=None):
                 units.append((0, 1))
             units.append((1, 3 if dah else 1))
     return np.concatenate([np.full(u * unit_samples, d, np.uint8) for d, u in units]) if units else np.zeros(0, np.uint8)
+
+
+def morse_codes(table=None):
+    """the keyer's character -> pattern table (selenite_tx_design_morse_codes): uint8 [256], the inverse of `table` (morse_table());
+    lower case as upper case, ' ' -> 1 (the word blank), a byte without a pattern -> 0 (skipped)"""
+    codes = np.zeros(256, np.uint8)
+    t = None if table is None else np.ascontiguousarray(table, np.uint8)
+    if t is not None and t.shape != (256,):
+        raise ValueError("morse_codes: table is uint8 [256]")
+    rc = lib().selenite_tx_design_morse_codes(codes.ctypes.data_as(u8p), None if t is None else t.ctypes.data_as(u8p))
+    if rc:
+        raise ValueError("selenite_tx_design_morse_codes: %d" % rc)
+    return codes
+
+
+def keyer_unit(wpm, fs_audio):
+    """audio samples per dit at `wpm` words per minute (PARIS timing): round(1.2 * fs_audio / wpm), at least 1"""
+    return int(lib().selenite_tx_keyer_unit(wpm, fs_audio))
 
 
 def ctcss_hz():
@@ -1981,6 +2039,123 @@ class Tx:
         """mean ms of the stage kernel alone over `iters` launches"""
         ms = C.c_float()
         rc = self.L.selenite_tx_time_in_stage_device(self.h, d_frames, kind, block_size, iters, C.byref(ms))
+        if rc:
+            raise RxError(rc, self.L.selenite_tx_error_string(self.h).decode())
+        return ms.value
+
+    def set_keyer(self, mode=KEYER_IAMBIC_B, unit=720, ring=256, codes=None, reserved=0):
+        """the keyer stage in front of the keyed CW path (selenite_tx_set_keyer; needs set_cw).  unit: audio samples per dit, one value
+        or [channels]; ring: text bytes per channel; codes: morse_codes() of another table, None = the built-in one.  Returns the status code."""
+        g = TxKeyerConfig()
+        g.struct_size, g.mode, g.ring, g.reserved = C.sizeof(TxKeyerConfig), int(mode), int(ring), int(reserved)
+        units = table = None
+        if np.ndim(unit):
+            units = np.ascontiguousarray(unit, np.uint32)
+            if units.shape != (self.cfg.channels,):
+                raise ValueError("unit: one value or [channels]")
+            g.unit = units.ctypes.data_as(u32p)
+        else:
+            g.unit_all = int(unit)
+        if codes is not None:
+            table = np.ascontiguousarray(codes, np.uint8)
+            if table.shape != (256,):
+                raise ValueError("codes: uint8 [256]")
+            g.codes = table.ctypes.data_as(C.POINTER(C.c_uint8))
+        rc = self.L.selenite_tx_set_keyer(self.h, C.byref(g))
+        if rc == 0:
+            self._keyer_ring = int(ring)
+        return rc
+
+    def clear_keyer(self):
+        """selenite_tx_set_keyer(S, NULL): the keyer off again"""
+        return self.L.selenite_tx_set_keyer(self.h, None)
+
+    def keyer_send(self, text, first_channel=0, n_channels=None):
+        """queue text: one str / bytes for every channel of the range, or a list of n_channels texts of one length.  Returns the status
+        code (LENGTH_ERROR: a channel lacks room; nothing was written)."""
+        n = self.cfg.channels - first_channel if n_channels is None else int(n_channels)
+        enc = lambda x: x.encode("latin-1") if isinstance(x, str) else bytes(x)
+        if isinstance(text, (str, bytes, bytearray)):
+            buf, per = np.frombuffer(enc(text), np.uint8), 0
+            ln = buf.size
+        else:
+            rows = [enc(x) for x in text]
+            if len(rows) != n or any(len(r) != len(rows[0]) for r in rows):
+                raise ValueError("keyer_send: n_channels texts of one length")
+            buf, per, ln = np.frombuffer(b"".join(rows), np.uint8), 1, len(rows[0])
+        return self.L.selenite_tx_keyer_send(self.h, int(first_channel), n, buf.ctypes.data if buf.size else None, ln, per)
+
+    def keyer_pending(self):
+        """characters queued and not yet begun, uint32 [channels]"""
+        a = np.zeros(self.cfg.channels, np.uint32)
+        rc = self.L.selenite_tx_keyer_pending(self.h, a.ctypes.data_as(u32p))
+        if rc:
+            raise RxError(rc, "selenite_tx_keyer_pending: the keyer is not configured (set_keyer)")
+        return a
+
+    def process_paddles(self, d_paddles, d_iq, d_side, block_size, q15=False):
+        """paddle bytes [channels][block_size] uint8 (bit 0 dit, bit 1 dah, bit 2 straight key; None: the text memory alone) -> the keyer
+        -> the keyed CW path: I/Q and sidetone as process_key writes them; device pointers, asynchronous.  Returns the status code."""
+        f = self.L.selenite_tx_process_paddles_q15_device if q15 else self.L.selenite_tx_process_paddles_f32_device
+        return f(self.h, d_paddles, d_iq, d_side, block_size)
+
+    def process_paddles_host(self, paddles, block_size=None, side=None, q15=False):
+        """the host entries: paddles [channels][n] uint8, or None with block_size -> (status, I/Q, sidetone or None)"""
+        if paddles is not None:
+            paddles = np.ascontiguousarray(paddles, np.uint8)
+            block_size = paddles.shape[1]
+        c, bs = self.cfg.channels, int(block_size)
+        dt = np.int16 if q15 else np.float32
+        out = np.zeros((c, bs * self.cfg.interp, 2), dt)
+        sd = None if side is None else np.array(side, dt, order="C")
+        f = self.L.selenite_tx_process_paddles_q15 if q15 else self.L.selenite_tx_process_paddles_f32
+        rc = f(self.h, None if paddles is None else paddles.ctypes.data, out.ctypes.data, None if sd is None else sd.ctypes.data, bs)
+        return rc, out, sd
+
+    def keyer_run(self, d_paddles, d_key, block_size):
+        """the stage alone: key bytes [channels][block_size] into d_key; device pointers, asynchronous.  Returns the status code."""
+        return self.L.selenite_tx_keyer_run_device(self.h, d_paddles, d_key, block_size)
+
+    def keyer_key_device(self):
+        """device pointer of the key bytes of the last paddle call, uint8 [channels][block_size] (None before it)"""
+        return self.L.selenite_tx_keyer_key_device(self.h)
+
+    def _keyer_arrays(self):
+        c = self.cfg.channels
+        a = {k: np.zeros(c, np.uint32) for k in KEYER_STATE_WORDS}
+        a["text"] = np.zeros((c, getattr(self, "_keyer_ring", 1)), np.uint8)
+        return a
+
+    @staticmethod
+    def _keyer_view(a):
+        v = TxKeyerStateView()
+        for k in KEYER_STATE_WORDS:
+            setattr(v, k, a[k].ctypes.data_as(u32p) if k in a else None)
+        v.text = a["text"].ctypes.data_as(C.POINTER(C.c_uint8)) if "text" in a else None
+        return v
+
+    def keyer_state(self):
+        a = self._keyer_arrays()
+        rc = self.L.selenite_tx_get_keyer_state(self.h, C.byref(self._keyer_view(a)))
+        if rc:
+            raise RxError(rc, "selenite_tx_get_keyer_state: the keyer is not configured (set_keyer)")
+        return a
+
+    def set_keyer_state(self, a):
+        """members that are missing from `a` are left as they are"""
+        want = self._keyer_arrays()
+        a = {k: np.ascontiguousarray(a[k], want[k].dtype) for k in want if k in a}
+        for k, x in a.items():
+            if x.shape != want[k].shape:
+                raise ValueError("%s: %s expected" % (k, want[k].shape))
+        rc = self.L.selenite_tx_set_keyer_state(self.h, C.byref(self._keyer_view(a)))
+        if rc:
+            raise RxError(rc, "selenite_tx_set_keyer_state: the keyer is not configured (set_keyer)")
+
+    def time_keyer_stage(self, d_paddles, block_size, iters):
+        """mean ms of the stage kernel alone over `iters` launches behind one untimed launch; the state moves"""
+        ms = C.c_float()
+        rc = self.L.selenite_tx_time_keyer_stage_device(self.h, d_paddles, block_size, iters, C.byref(ms))
         if rc:
             raise RxError(rc, self.L.selenite_tx_error_string(self.h).decode())
         return ms.value
