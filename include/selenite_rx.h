@@ -30,6 +30,7 @@
  *   -> arm_biquad_cascade_df1_f32 (CW narrow filter)
  *   -> [optional tap: Goertzel tone-detector bank (CTCSS, DTMF, selcall), selenite_rx_set_tones]
  *   -> [optional tap: arm_power_f32 per DSP block -> Morse decoder (CW skimmer), selenite_rx_set_cwdec]
+ *   -> [optional tap: two arm_biquad_cascade_df1_f32 + arm_power_f32 per tick -> FSK teleprinter decoder (RTTY skimmer), selenite_rx_set_fskdec]
  *   -> [optional: arm_biquad_cascade_df1_f32 audio filter (notch, de-emphasis, EQ), selenite_rx_set_afilt]
  *   -> [optional: arm_lms_norm_f32 noise reduction / automatic notch, selenite_rx_set_nr]
  *   -> [optional: arm_power_f32 per DSP block -> level meter -> squelch decision, selenite_rx_set_meter]
@@ -558,6 +559,81 @@ typedef struct selenite_rx_cwdec_state_view {
     uint8_t *text;            /* [channels][ring] */
 } selenite_rx_cwdec_state_view;
 
+/* ---- FSK teleprinter decoder, an RTTY skimmer (a TAP on the un-scaled audio behind the
+ * demodulator and the CW filter, in front of the audio filter, NLMS, the level meter and the AGC; off by default) -----------------------
+ * The stage is a tap, off by default, on the un-scaled audio behind the demodulator and the CW filter (step 4).  That is the tone bank's and
+ * the Morse decoder's position, in front of 4a / 4b / 4c / the AGC.  It works in every mode and every `arith` mode, and it changes none of
+ * the audio.  It neither raises nor clears SELENITE_RX_NANINF.
+ * One tick is T = tick consecutive audio samples, 4 <= T <= 256.  T must divide n = block / decim, otherwise the call returns
+ * SELENITE_RX_LENGTH_ERROR, as the noise blanker's frame does.  So ticks never straddle DSP blocks or calls, and nothing is left pending.
+ * Every float operation is rounded to f32, with no contraction and denormals kept.  These are the meter's rules.
+ * Per channel and tick, with x the tick's samples:
+ *   two arm_biquad_cascade_df1_f32 instances of ONE section each, coefficients {b0,b1,b2,a1,a2} = mark[5] / space[5] (one set for all channels),
+ *   state {x1,x2,y1,y2} each, running on across ticks, blocks and calls:
+ *       per sample:  acc = b0*x; acc = acc + b1*x1; acc = acc + b2*x2; acc = acc + a1*y1; acc = acc + a2*y2;  (each product rounded, then the sum)
+ *                    x2 = x1; x1 = x; y2 = y1; y1 = acc
+ *   pm = arm_power_f32(ym, T);  ps = arm_power_f32(ys, T);  pw = arm_power_f32(x, T)        (from +0.0f, ascending; no division)
+ *   if (reverse) swap(pm, ps)
+ *   if (pm <= FLT_MAX && ps <= FLT_MAX && pw <= FLT_MAX) {           (false for NaN: the followers stay)
+ *       d = pm - em; t = alpha*d; em = em + t;      es, ew likewise from ps, pw          (the AGC's form)
+ *   }
+ *   tot = em + es;  dd = em - es;  th = hyst*tot;  q = frac*ew
+ *   present = tot > q && tot > min_power && tot <= FLT_MAX
+ *   prev = lvl
+ *   if (!present) lvl = 1;  else if (dd > th) lvl = 1;  else if (-dd > th) lvl = 0;      (else lvl stays; 1 = mark = idle)
+ *   if (k == 0) { if (prev == 1 && lvl == 0) { k = 1; t_q8 = 0; shift = 0; } }            (start edge; nothing is sampled in this tick)
+ *   else {
+ *       t_q8 += 256
+ *       if (t_q8 >= (k-1)*bit + (bit >> 1)) {                                             (centre of bit k-1; bit: this channel's, Q8 ticks)
+ *           if (k == 1)      { k = lvl ? 0 : 2; }                                         (a start bit that did not last: false start)
+ *           else if (k <= 6) { shift |= lvl << (k-2); k += 1; }                           (five data bits, LSB first)
+ *           else { if (lvl) { c = shift;
+ *                             if (c == 31) figs = 0; else if (c == 27) figs = 1;
+ *                             else { b = table[figs*32 + c]; if (b) emit(b); if (usos && c == 4) figs = 0; } }
+ *                  else ferr += 1;                                                         (framing error: nothing is emitted)
+ *                  k = 0; }
+ *       }
+ *   }
+ *   emit(b):  text[count % ring] = b;  count += 1
+ * State per channel after set_fskdec / selenite_rx_reset: filt[2][4], em, es, ew: +0.0f; lvl: 1; k, t_q8, shift, figs, ferr: 0; bit: the
+ * config's bit_q8; count: 0 (u64); text[ring]: 0.  `bit` is a state row: through set_fskdec_state every channel can run at its own speed,
+ * the way `unit` does for the Morse decoder.  A non-finite sample poisons that channel's filters until reset or set_fskdec_state: the three
+ * followers stay where they stood.  The state moves with ChanRange.first.  set_mode and the other setters leave it alone.
+ * `table` is 64 bytes, copied: letters then figures, indexed by the 5-bit code; a 0 byte emits nothing.
+ * One set of parameters, one coefficient pair and one table for all channels. */
+typedef struct selenite_rx_fskdec_config {
+    uint32_t struct_size;     /* = sizeof(selenite_rx_fskdec_config) (this struct's own growth path) */
+    uint32_t tick;            /* T: 4 .. 256 audio samples; must divide cfg.block / cfg.decim (SELENITE_RX_LENGTH_ERROR) */
+    uint32_t bit_q8;          /* a bit in Q8 ticks, 8 * 256 .. 1024 * 256: every channel's `bit` after set_fskdec / reset */
+    uint32_t reverse;         /* 0 / 1: the tones swapped (mark is the `space` filter) */
+    uint32_t usos;            /* 0 / 1: unshift on space */
+    uint32_t ring;            /* a power of two, 16 .. 65536: characters kept per channel */
+    float mark[5];            /* {b0, b1, b2, a1, a2} in CMSIS's sign convention (selenite_rx_design_fsk); finite */
+    float space[5];
+    float alpha;              /* the followers' rate: finite, in (0, 1] */
+    float hyst;               /* finite, in [0, 1) */
+    float frac;               /* finite, in [0, 1] */
+    float min_power;          /* finite, >= 0 */
+    const uint8_t *table;     /* [64], copied; NULL selects the built-in ITA2 / US-TTY table (selenite_rx_design_ita2) */
+} selenite_rx_fskdec_config;
+
+/* The stage's whole state.  NULL members are skipped. */
+typedef struct selenite_rx_fskdec_state_view {
+    float *filt;              /* [channels][2][4]: mark then space, {x1, x2, y1, y2} each */
+    float *em;                /* [channels] the three followers: mark, space (behind `reverse`), the whole band */
+    float *es;
+    float *ew;
+    uint32_t *lvl;            /* [channels] 1 = mark = idle */
+    uint32_t *k;              /* [channels] 0: idle; 1: in the start bit; 2 .. 6: before data bit k - 2; 7: before the stop bit */
+    uint32_t *t_q8;           /* [channels] Q8 ticks since the start edge */
+    uint32_t *shift;          /* [channels] the data bits so far, LSB first */
+    uint32_t *figs;           /* [channels] 0 / 1: letters / figures */
+    uint32_t *ferr;           /* [channels] framing errors since set_fskdec / reset */
+    uint32_t *bit;            /* [channels] this channel's bit length, Q8 ticks */
+    uint64_t *count;          /* [channels] characters emitted since set_fskdec / reset */
+    uint8_t *text;            /* [channels][ring] */
+} selenite_rx_fskdec_state_view;
+
 typedef struct selenite_rx_instance selenite_rx_instance;  /* opaque; state lives in HBM */
 
 /* ---- instance life cycle ------------------------------------------------------------- */
@@ -853,6 +929,30 @@ const uint8_t *selenite_rx_cwdec_text_device(const selenite_rx_instance *S);
 const uint64_t *selenite_rx_cwdec_count_device(const selenite_rx_instance *S);
 const uint32_t *selenite_rx_cwdec_unit_device(const selenite_rx_instance *S);
 
+/* FSK teleprinter decoder (the law: selenite_rx_fskdec_config above).  f == NULL removes the stage and releases its buffers.  Puts the
+ * stage's state at its start.  Drains the instance's stream first.  SELENITE_RX_ARGUMENT_ERROR (a field outside its range as the struct
+ * states them, a wrong struct_size) and SELENITE_RX_LENGTH_ERROR (tick does not divide cfg.block / cfg.decim) leave the instance as it
+ * was, a working stage included.  SELENITE_RX_DEVICE_ERROR is different: the old stage is released before the new rows are allocated, so a
+ * failed allocation leaves the instance with NO stage (as after f == NULL).  selenite_rx_set_mode and every other setter leave it alone;
+ * selenite_rx_reset returns it to its state after set_fskdec and keeps the parameters and the table.  Every process entry point runs it
+ * once per call (f32 and int16 slots, device and host pointers, the timing calls, global phase 1, selenite_rx_global_process_f32_device
+ * -- not phase 2); the state rows of a channel chunk of a host-pointer call move with its first channel.  With the stage on, the fused
+ * kernels run with their own AGC off and the generic AGC kernel finishes the call, as with NLMS.  With the stage off no launch, byte,
+ * allocation or output of any call changes. */
+int selenite_rx_set_fskdec(selenite_rx_instance *S, const selenite_rx_fskdec_config *f);
+/* Host copies of the state.  Drain the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the stage is off. */
+int selenite_rx_get_fskdec_state(selenite_rx_instance *S, const selenite_rx_fskdec_state_view *dst);
+int selenite_rx_set_fskdec_state(selenite_rx_instance *S, const selenite_rx_fskdec_state_view *src);
+/* Host copies of what a reader wants: text [channels][ring], count, ferr, lvl [channels].  Character i of a channel (i < count, i >=
+ * count - ring) is text[i % ring].  NULL arguments are skipped.  Drains the instance's stream.  SELENITE_RX_ARGUMENT_ERROR while the
+ * stage is off. */
+int selenite_rx_get_fskdec(selenite_rx_instance *S, uint8_t *text, uint64_t *count, uint32_t *ferr, uint32_t *lvl);
+/* The rows on the device, readable on the instance's stream behind a call; NULL while the stage is off; valid until the next
+ * selenite_rx_set_fskdec or selenite_rx_free. */
+const uint8_t *selenite_rx_fskdec_text_device(const selenite_rx_instance *S);
+const uint64_t *selenite_rx_fskdec_count_device(const selenite_rx_instance *S);
+const uint32_t *selenite_rx_fskdec_lvl_device(const selenite_rx_instance *S);
+
 void *selenite_rx_device_alloc(size_t bytes);          /* hipMalloc; NULL on failure */
 void  selenite_rx_device_free(void *dptr);
 int   selenite_rx_memcpy_h2d(void *dptr, const void *hptr, size_t bytes);
@@ -978,6 +1078,15 @@ uint32_t selenite_rx_ctcss_hz(double hz[50]);
  * A-Z, 0-9, . (.-.-.-) , (--..--) ? (..--..) / (-..-.) = (-...-) + (.-.-.) - (-....-) @ (.--.-.); every other index, 0 (the overflow
  * character) included, is `unknown`.  Host only. */
 int selenite_rx_design_morse(uint8_t table[256], uint8_t unknown);
+
+/* The FSK decoder's tone filters: two constant-peak-gain band-pass sections, one at f_mark and one at f_space (cycles per audio sample, in
+ * (0, 0.5)), each `bandwidth` wide (cycles per audio sample, > 0): w = 2 pi f0, alpha = sin w / (2 f0 / bandwidth),
+ * {alpha, 0, -alpha, 2 cos w, -(1 - alpha)} / (1 + alpha) in CMSIS's sign convention ({b0, b1, b2, a1, a2}); double arithmetic, rounded
+ * once.  SELENITE_RX_ARGUMENT_ERROR for a NULL pointer or an argument that is not finite or outside its range.  Host only. */
+int selenite_rx_design_fsk(double f_mark, double f_space, double bandwidth, float mark[5], float space[5]);
+/* The FSK decoder's built-in table, ITA2 with the US-TTY figures: table[code] the letter, table[32 + code] the figure of the 5-bit code
+ * (bit 0 sent first); 0 where a code prints nothing (NUL, LTRS, FIGS); CR, LF, BEL (7) and the blank as themselves.  Host only. */
+int selenite_rx_design_ita2(uint8_t table[64]);
 
 int selenite_rx_abi_version(void);
 

@@ -1,6 +1,6 @@
 // rx_api.hip -- the C-ABI of include/selenite_rx.h over the HIP kernels: instance setup and teardown, the accessors, and the
 // device-pointer process entry points.  The dispatcher behind them is rx_dispatch.hip, the host-pointer calls rx_hostpipe.hip, the timing
-// calls rx_timing.hip; each stage's host side sits next to its kernels (rx_tones.hip, rx_cwdec.hip, rx_afilt.hip, rx_nlms.hip, rx_meter.hip, rx_out.hip, rx_spectrum.hip, rx_iqc.hip, rx_nb.hip).
+// calls rx_timing.hip; each stage's host side sits next to its kernels (rx_tones.hip, rx_cwdec.hip, rx_fskdec.hip, rx_afilt.hip, rx_nlms.hip, rx_meter.hip, rx_out.hip, rx_spectrum.hip, rx_iqc.hip, rx_nb.hip).
 //
 // Host side of the drop-in boundary: mirrors the CMSIS-DSP init/process convention
 // (arm_fir_decimate_init_f32.c:63-101 validation and state clearing; process calls return void)
@@ -64,6 +64,7 @@ static void free_device(selenite_rx_instance *S)
              S->d_io_in, S->d_io_out, S->d_lo, S->pipe.d_in[0], S->pipe.d_in[1], S->pipe.d_out[0], S->pipe.d_out[1]);
     S->tones.release();
     S->cwdec.release();
+    S->fskdec.release();
     S->afilt.release();
     S->nr.release();
     S->meter.release();
@@ -105,6 +106,7 @@ static int reset_state(selenite_rx_instance *S)
     S->phase_host = 0;
     if (int rc = S->tones.init_state(S)) return rc;
     if (int rc = S->cwdec.init_state(S)) return rc;
+    if (int rc = S->fskdec.init_state(S)) return rc;
     if (int rc = S->afilt.init_state(S)) return rc;
     if (int rc = S->nr.init_state(S)) return rc;
     if (int rc = S->meter.init_state(S)) return rc;

@@ -210,6 +210,39 @@ extern "C" int selenite_tx_design_keyshape(uint32_t ns_taps, float *coeffs)
     return SELENITE_RX_SUCCESS;
 }
 
+// the FSK decoder's tone filters (rx_fskdec.hip): the constant-peak-gain band-pass of design_biquad's family, Q = f0 / bandwidth
+extern "C" int selenite_rx_design_fsk(double f_mark, double f_space, double bandwidth, float mark[5], float space[5])
+{
+    if (!mark || !space) return SELENITE_RX_ARGUMENT_ERROR;
+    if (!(std::isfinite(bandwidth) && bandwidth > 0.0)) return SELENITE_RX_ARGUMENT_ERROR;
+    const double f[2] = { f_mark, f_space };
+    float *out[2] = { mark, space };
+    for (double f0 : f)
+        if (!(std::isfinite(f0) && f0 > 0.0 && f0 < 0.5)) return SELENITE_RX_ARGUMENT_ERROR;
+    for (int i = 0; i < 2; ++i) {
+        const double w = 2.0 * kPi * f[i], alpha = std::sin(w) / (2.0 * f[i] / bandwidth), a0 = 1.0 + alpha;
+        out[i][0] = (float)(alpha / a0);
+        out[i][1] = 0.0f;
+        out[i][2] = (float)(-alpha / a0);
+        out[i][3] = (float)(2.0 * std::cos(w) / a0);
+        out[i][4] = (float)(-(1.0 - alpha) / a0);
+    }
+    return SELENITE_RX_SUCCESS;
+}
+
+// the FSK decoder's table (rx_fskdec.hip): ITA2 letters, then the US-TTY figures, by the 5-bit code (bit 0 sent first)
+extern "C" int selenite_rx_design_ita2(uint8_t table[64])
+{
+    static const char kLetters[33] = "\0E\nA SIU\rDRJNFCKTZLWHYPQOBG\0MXV";
+    static const char kFigures[33] = "\0" "3\n- \a87\r$4',!:(5\")2#6019?&\0./;";
+    if (!table) return SELENITE_RX_ARGUMENT_ERROR;
+    for (int i = 0; i < 32; ++i) {
+        table[i] = (uint8_t)kLetters[i];
+        table[32 + i] = (uint8_t)kFigures[i];
+    }
+    return SELENITE_RX_SUCCESS;
+}
+
 // include/selenite_tx_keyer.h: character -> element pattern, the inverse of selenite_rx_design_morse's table (NULL: the built-in one).
 // The smallest pattern >= 2 of a character wins; the filler table[0] has none; a lower-case letter takes its upper-case letter's; the
 // blank is 1 (the keyer's word blank); every other byte is 0 (the keyer skips and counts it).

@@ -1,9 +1,9 @@
 // rx_dispatch.hip -- the one dispatcher behind every process entry point: which kernels serve a call, over which channels
 // (ChanRange), from which stream positions (CallStart).  Two host-side functions decide, the launchers here execute: select() (rx_select.h)
 // names the kernel of a launch, route() (rx_route.h) its way through the stages -- which of them run, on which buffer, what finishes it.
-// The nine stages hook in here and nowhere else:
+// The ten stages hook in here and nowhere else:
 //   run_front        the spectrum tap, the I/Q correction and the noise blanker in front of the chain;
-//   run_part         the tone detector, the Morse decoder, the audio filter, NLMS and the level meter in front of the AGC, the meter's gate behind it;
+//   run_part         the tone detector, the Morse decoder, the FSK decoder, the audio filter, NLMS and the level meter in front of the AGC, the meter's gate behind it;
 //   with_out_stage   the output stage behind the chain.
 // A new stage in front of the AGC is one line in the route (its flag in StagesOn: it then counts in `unscaled`, and in what select() is told)
 // and one in the executor (its launch in run_part, at its place among the others); one in front of the chain is one line in run_front.
@@ -18,7 +18,7 @@ static StagesOn stages_on(const selenite_rx_instance *S)
 {
     StagesOn on;
     on.tones = S->tones.on; on.afilt = S->afilt.on; on.nr = S->nr.kind != SELENITE_RX_NR_OFF; on.meter = S->meter.on;
-    on.cwdec = S->cwdec.on;
+    on.cwdec = S->cwdec.on; on.fskdec = S->fskdec.on;
     return on;
 }
 
@@ -250,6 +250,8 @@ static int run_part(selenite_rx_instance *S, ChanRange r, const Decision &d, Cal
     if (t.run.tones) HIPCHK(S, launch_tones(S->tones.params(r, p, at.offset / g.block), audio, st));
     // step 4-d: the Morse decoder reads the same audio, one tick per DSP block of this launch
     if (t.run.cwdec) HIPCHK(S, launch_cwdec(S->cwdec.params(r, p), audio, st));
+    // step 4-r: the FSK decoder reads the same audio, n / T ticks per DSP block of this launch
+    if (t.run.fskdec) HIPCHK(S, launch_fskdec(S->fskdec.params(r, p), audio, st));
     // step 4a: the audio filter in place on the un-scaled audio of this launch (a part of a cut call: its dst offset, the full stride)
     if (t.run.afilt) HIPCHK(S, launch_afilt(S->afilt.params(r, p), audio, st));
     // step 4b: NLMS in place on the un-scaled audio (phase 1 of a global gain: before the envelope)

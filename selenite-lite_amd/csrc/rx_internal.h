@@ -407,6 +407,43 @@ struct __attribute__((visibility("hidden"))) CwdecStage {
     CwdecParams params(ChanRange r, const RxParams &p) const;   // the stage's view of a launch: the channels and the audio geometry of `p`
 };
 
+// ---- FSK teleprinter decoder (rx_fskdec.hip): two one-section arm_biquad_cascade_df1_f32 tone filters and arm_power_f32 per tick of the
+// un-scaled audio -> three followers -> level with hysteresis -> start / data / stop bit clock -> ITA2 text, a tap at the tone bank's place ----
+struct FskdecParams {
+    uint32_t channels;     // channels of this launch (a ChanRange: the state rows and `text` are offset to it)
+    uint32_t n;            // audio samples of a DSP block: block / decim
+    uint32_t nblk;         // DSP blocks per channel in this launch
+    uint32_t stride;       // audio samples between consecutive channels (RxParams::out_stride)
+    uint32_t tick;         // T: divides n
+    uint32_t reverse, usos;
+    uint32_t ring;         // a power of two
+    float mark[5], space[5];   // {b0, b1, b2, a1, a2}
+    float alpha, hyst, frac, min_power;
+    const uint8_t *table;  // [64]
+    float *filt;           // [C][2][4]
+    float *em, *es, *ew;   // [C] each
+    uint32_t *lvl, *k, *t_q8, *shift, *figs, *ferr, *bit;      // [C] each
+    uint64_t *count;       // [C]
+    uint8_t *text;         // [C][ring]
+};
+hipError_t launch_fskdec(const FskdecParams &q, const float *audio, hipStream_t st);
+// the stage's part of the instance (selenite_rx_set_fskdec): on = false: no stage, no buffers
+struct __attribute__((visibility("hidden"))) FskdecStage {
+    bool on = false;
+    uint32_t tick = 0, bit_q8 = 0, reverse = 0, usos = 0, ring = 0;
+    float mark[5] = {}, space[5] = {};
+    float alpha = 0.0f, hyst = 0.0f, frac = 0.0f, min_power = 0.0f;
+    uint8_t *d_table = nullptr;                             // [64]
+    float *d_filt = nullptr;                                // [channels][2][4]
+    float *d_em = nullptr, *d_es = nullptr, *d_ew = nullptr;    // [channels] each
+    uint32_t *d_lvl = nullptr, *d_k = nullptr, *d_t_q8 = nullptr, *d_shift = nullptr, *d_figs = nullptr, *d_ferr = nullptr, *d_bit = nullptr;
+    uint64_t *d_count = nullptr;                            // [channels]
+    uint8_t *d_text = nullptr;                              // [channels][ring]
+    void release();                                         // frees the buffers: no stage
+    int init_state(selenite_rx_instance *S);                // the state set_fskdec leaves
+    FskdecParams params(ChanRange r, const RxParams &p) const;  // the stage's view of a launch: the channels and the audio geometry of `p`
+};
+
 // ---- fused fast paths (rx_fused.hip); return false when the configuration is not covered ----
 struct FusedPlan {
     SelPlan sel;                  // what select() reads: the shape (kind 0 = none), dense or not, which operands exist (rx_select.h)
@@ -502,6 +539,7 @@ struct selenite_rx_instance {
     int force_generic = 0;             // SELENITE_RX_FORCE_GENERIC=1 (tests cross-check both paths)
     srx::TonesStage tones;             // tone-detector bank, a tap behind the demodulator / CW filter, in front of the audio filter (rx_tones.hip)
     srx::CwdecStage cwdec;             // Morse decoder, a tap at the tone bank's place (rx_cwdec.hip)
+    srx::FskdecStage fskdec;           // FSK teleprinter decoder, a tap at the tone bank's place (rx_fskdec.hip)
     srx::AfiltStage afilt;             // audio biquad filter, behind the demodulator / CW filter, in front of NLMS (rx_afilt.hip)
     srx::NrStage nr;                   // NLMS noise reduction / automatic notch, in front of the AGC (rx_nlms.hip)
     srx::MeterStage meter;             // signal-level meter and squelch, between NLMS and the AGC; its gate behind the AGC (rx_meter.hip)

@@ -10,11 +10,11 @@ namespace srx {
 // all: a whole call; 1 / 2: the two halves of a global-gain call around the exchange of the envelopes (phase 2 only applies the gain)
 enum Phase { kAll, kPhase1, kPhase2 };
 
-// The stages in front of the AGC.  Each of them wants the un-scaled f32 audio of the launch: the tone detector, the Morse decoder and the level meter read it,
+// The stages in front of the AGC.  Each of them wants the un-scaled f32 audio of the launch: the tone detector, the Morse decoder, the FSK decoder and the level meter read it,
 // the audio filter and NLMS run in place on it.
 struct StagesOn {
-    bool tones = false, afilt = false, nr = false, meter = false, cwdec = false;
-    bool any() const { return tones || afilt || meter || nr || cwdec; }
+    bool tones = false, afilt = false, nr = false, meter = false, cwdec = false, fskdec = false;
+    bool any() const { return tones || afilt || meter || nr || cwdec || fskdec; }
 };
 
 struct RouteFacts {

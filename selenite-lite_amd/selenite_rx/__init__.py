@@ -173,6 +173,22 @@ class CwdecStateView(C.Structure):
 CWDEC_DEFAULTS = dict(peak_attack=0.5, peak_decay=0.002, floor_attack=0.25, floor_decay=0.002, on_frac=0.4, off_frac=0.25, snr=4.0,
                       min_power=1e-8, debounce=2, adapt=1, track=2, unit_min=2 * 256, unit_init=10 * 256, unit_max=64 * 256, ring=256)
 
+class FskdecConfig(C.Structure):
+    """struct selenite_rx_fskdec_config."""
+    _fields_ = [("struct_size", C.c_uint32), ("tick", C.c_uint32), ("bit_q8", C.c_uint32), ("reverse", C.c_uint32), ("usos", C.c_uint32),
+                ("ring", C.c_uint32), ("mark", C.c_float * 5), ("space", C.c_float * 5), ("alpha", C.c_float), ("hyst", C.c_float),
+                ("frac", C.c_float), ("min_power", C.c_float), ("table", u8p)]
+
+
+class FskdecStateView(C.Structure):
+    """struct selenite_rx_fskdec_state_view."""
+    _fields_ = [("filt", f32p), ("em", f32p), ("es", f32p), ("ew", f32p), ("lvl", u32p), ("k", u32p), ("t_q8", u32p), ("shift", u32p),
+                ("figs", u32p), ("ferr", u32p), ("bit", u32p), ("count", u64p), ("text", u8p)]
+
+
+# the documented defaults of Rx.set_fskdec (45.45 baud at 12 kHz of audio and ticks of 16 samples: 16.5 ticks per bit)
+FSKDEC_DEFAULTS = dict(tick=16, bit_q8=4224, reverse=0, usos=1, ring=256, alpha=0.25, hyst=0.1, frac=0.35, min_power=1e-6)
+
 # every symbol include/selenite_rx.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
     "selenite_rx_init", "selenite_rx_free", "selenite_rx_set_mode", "selenite_rx_status",
@@ -204,6 +220,9 @@ ABI_SYMBOLS = [
     "selenite_rx_tones_tone_device", "selenite_rx_tones_power_device", "selenite_rx_design_tones", "selenite_rx_ctcss_hz",
     "selenite_rx_set_cwdec", "selenite_rx_get_cwdec_state", "selenite_rx_set_cwdec_state", "selenite_rx_get_cwdec",
     "selenite_rx_cwdec_text_device", "selenite_rx_cwdec_count_device", "selenite_rx_cwdec_unit_device", "selenite_rx_design_morse",
+    "selenite_rx_set_fskdec", "selenite_rx_get_fskdec_state", "selenite_rx_set_fskdec_state", "selenite_rx_get_fskdec",
+    "selenite_rx_fskdec_text_device", "selenite_rx_fskdec_count_device", "selenite_rx_fskdec_lvl_device", "selenite_rx_design_fsk",
+    "selenite_rx_design_ita2",
 ]
 
 class TxConfig(C.Structure):
@@ -429,7 +448,8 @@ def _signatures():
     # the stages: set_X takes the config, get_X_state / set_X_state the view
     for _x, _cfg, _view in (("nr", NrConfig, NrStateView), ("spectrum", SpecConfig, SpecStateView), ("nb", NbConfig, NbStateView),
                             ("iqc", IqcConfig, IqcStateView), ("meter", MeterConfig, MeterStateView), ("afilt", AfiltConfig, AfiltStateView),
-                            ("tones", TonesConfig, TonesStateView), ("cwdec", CwdecConfig, CwdecStateView)):
+                            ("tones", TonesConfig, TonesStateView), ("cwdec", CwdecConfig, CwdecStateView),
+                            ("fskdec", FskdecConfig, FskdecStateView)):
         sig("selenite_rx_", "set_%s" % _x, [vp, P(_cfg)])
         sig("selenite_rx_", "get_%s_state set_%s_state" % (_x, _x), [vp, P(_view)])
     sig("selenite_rx_", "set_out", [vp, P(OutConfig)])
@@ -438,7 +458,7 @@ def _signatures():
     sig("selenite_rx_", "design_interp", [f32p, u32, u32, f64])
     sig("selenite_rx_", "get_spectrum", [vp, f32p, u64p])
     sig("selenite_rx_", "spectrum_device meter_level_device meter_open_device tones_tone_device tones_power_device "
-         "cwdec_text_device cwdec_count_device cwdec_unit_device", [vp], vp)
+         "cwdec_text_device cwdec_count_device cwdec_unit_device fskdec_text_device fskdec_count_device fskdec_lvl_device", [vp], vp)
     sig("selenite_rx_", "spectrum_twiddles", [f32p, u32])
     sig("selenite_rx_", "design_window", [f32p, u32, C.c_int])
     sig("selenite_rx_", "set_afilt_coeffs", [vp, u32, u32, f32p])
@@ -449,6 +469,9 @@ def _signatures():
     sig("selenite_rx_", "ctcss_hz", [P(f64)], u32)
     sig("selenite_rx_", "get_cwdec", [vp, u8p, u64p, u32p, u32p])
     sig("selenite_rx_", "design_morse", [u8p, u8])
+    sig("selenite_rx_", "get_fskdec", [vp, u8p, u64p, u32p, u32p])
+    sig("selenite_rx_", "design_fsk", [f64, f64, f64, f32p, f32p])
+    sig("selenite_rx_", "design_ita2", [u8p])
 
     sig("selenite_tx_", "init", [P(vp), P(TxConfig)])
     sig("selenite_tx_", "free status sync reset", [vp])
@@ -575,6 +598,26 @@ def morse_table(unknown="#"):
     rc = lib().selenite_rx_design_morse(t.ctypes.data_as(u8p), ord(unknown) if isinstance(unknown, str) else int(unknown))
     if rc:
         raise ValueError("selenite_rx_design_morse: %d" % rc)
+    return t
+
+
+def fsk_bandpass(f_mark, f_space, bandwidth):
+    """the FSK decoder's tone filters (selenite_rx_design_fsk): (mark, space), float32 [5] each, {b0, b1, b2, a1, a2} of the
+    constant-peak-gain band-pass at f_mark / f_space, `bandwidth` wide; all three in cycles per sample of the audio rate"""
+    m, s = np.empty(5, np.float32), np.empty(5, np.float32)
+    rc = lib().selenite_rx_design_fsk(float(f_mark), float(f_space), float(bandwidth), _fp(m), _fp(s))
+    if rc:
+        raise ValueError("selenite_rx_design_fsk: %d" % rc)
+    return m, s
+
+
+def ita2_table():
+    """the FSK decoder's built-in table (selenite_rx_design_ita2): uint8 [64], ITA2 letters then the US-TTY figures by the 5-bit code; 0
+    where a code prints nothing"""
+    t = np.zeros(64, np.uint8)
+    rc = lib().selenite_rx_design_ita2(t.ctypes.data_as(u8p))
+    if rc:
+        raise ValueError("selenite_rx_design_ita2: %d" % rc)
     return t
 
 

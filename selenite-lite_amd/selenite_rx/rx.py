@@ -5,8 +5,8 @@ import numpy as np
 
 from . import RxError, _fp, lib, ring_text
 from ._state import channel_rows, dtypes, get_state, set_state
-from . import (ARGUMENT_ERROR, CWDEC_DEFAULTS, LENGTH_ERROR, NR_OFF, OUT_MONO, SQ_ABOVE, SUCCESS, AfiltConfig, AfiltStateView,
-                  CwdecConfig, CwdecStateView, IqcConfig, IqcStateView, MeterConfig, MeterStateView, NbConfig, NbStateView, NrConfig,
+from . import (ARGUMENT_ERROR, CWDEC_DEFAULTS, FSKDEC_DEFAULTS, LENGTH_ERROR, NR_OFF, OUT_MONO, SQ_ABOVE, SUCCESS, AfiltConfig, AfiltStateView,
+                  CwdecConfig, CwdecStateView, FskdecConfig, FskdecStateView, IqcConfig, IqcStateView, MeterConfig, MeterStateView, NbConfig, NbStateView, NrConfig,
                   NrStateView, OutConfig, SpecConfig, SpecStateView, StateView, TonesConfig, TonesStateView, i16p, u8p, u32p, u64p)
 
 
@@ -19,7 +19,7 @@ class Rx:
         self.cfg = cfg
         self.h = C.c_void_p()
         # what Python remembers of each stage to size its state arrays (None: the stage is off); _set_stage keeps them
-        self._nr = self._out = self._spec = self._nb = self._iqc = self._meter = self._afilt = self._tones = self._cwdec = None
+        self._nr = self._out = self._spec = self._nb = self._iqc = self._meter = self._afilt = self._tones = self._cwdec = self._fskdec = None
         rc = self.L.selenite_rx_init(C.byref(self.h), C.byref(cfg))
         if rc != SUCCESS:
             raise RxError(rc, self.L.selenite_rx_error_string(None).decode())
@@ -565,6 +565,82 @@ class Rx:
     def cwdec_unit_device(self):
         """device address of the unit row, u32 [channels] (None while the stage is off)"""
         return self.L.selenite_rx_cwdec_unit_device(self.h)
+
+    # -- FSK teleprinter decoder (selenite_rx_set_fskdec) ------------------------------------------------
+    FSKDEC_TYPES = dtypes(FskdecStateView)
+
+    def set_fskdec(self, mark=None, space=None, table=None, **par):
+        """Put the FSK teleprinter decoder on the un-scaled audio of every channel (a tap at the tone bank's place: it changes no audio), or
+        remove it (set_fskdec(None)).  mark, space: float32 [5] each (fsk_bandpass).  par: the fields of selenite_rx_fskdec_config; the
+        defaults are FSKDEC_DEFAULTS: tick 16, bit_q8 4224 (16.5 ticks: 45.45 baud at 12 kHz), reverse 0, usos 1, ring 256, alpha 0.25,
+        hyst 0.1, frac 0.35, min_power 1e-6.  table: uint8 [64] (None: ita2_table()).  Puts the stage's state at its start.  Raises
+        RxError on a bad field; the instance is then left as it was."""
+        if mark is None or mark is False:
+            return self._set_stage("_fskdec", self.L.selenite_rx_set_fskdec, None, None)
+        unknown = set(par) - set(FSKDEC_DEFAULTS)
+        if unknown:
+            raise TypeError("set_fskdec: unknown fields %s" % sorted(unknown))
+        m, s = np.ascontiguousarray(mark, np.float32), np.ascontiguousarray(space, np.float32)
+        if m.shape != (5,) or s.shape != (5,):
+            raise RxError(ARGUMENT_ERROR, "set_fskdec: mark / space is not [5]")
+        p = dict(FSKDEC_DEFAULTS, **par)
+        g = FskdecConfig()
+        g.struct_size = C.sizeof(FskdecConfig)
+        for k, v in p.items():
+            setattr(g, k, float(v) if isinstance(FSKDEC_DEFAULTS[k], float) else int(v))
+        g.mark[:], g.space[:] = m.tolist(), s.tolist()
+        t = None
+        if table is not None:
+            t = np.ascontiguousarray(table, np.uint8)
+            if t.shape != (64,):
+                raise RxError(ARGUMENT_ERROR, "set_fskdec: table is not [64]")
+            g.table = t.ctypes.data_as(u8p)
+        self._set_stage("_fskdec", self.L.selenite_rx_set_fskdec, g, int(p["ring"]))
+
+    def _fskdec_shapes(self):
+        ch, ring = self.cfg.channels, self._on("_fskdec", "FSK decoder")
+        return dict(channel_rows(FskdecStateView, ch), filt=(ch, 2, 4), text=(ch, ring))
+
+    def fskdec_state(self):
+        """dict(filt f32 [channels][2][4]; em, es, ew f32; lvl, k, t_q8, shift, figs, ferr, bit u32; count u64, each [channels]; text u8
+        [channels][ring]); drains the stream"""
+        return get_state(self.L.selenite_rx_get_fskdec_state, self.h, FskdecStateView, self._fskdec_shapes())
+
+    def set_fskdec_state(self, d):
+        set_state(self.L.selenite_rx_set_fskdec_state, self.h, FskdecStateView, self._fskdec_shapes(), d)
+
+    def fskdec(self):
+        """(text u8 [channels][ring], count u64, ferr u32, lvl u32 [channels]): selenite_rx_get_fskdec; drains the stream"""
+        sh = self._fskdec_shapes()
+        text, count = np.zeros(sh["text"], np.uint8), np.zeros(sh["count"], np.uint64)
+        ferr, lvl = np.zeros(sh["ferr"], np.uint32), np.zeros(sh["lvl"], np.uint32)
+        rc = self.L.selenite_rx_get_fskdec(self.h, text.ctypes.data_as(u8p), count.ctypes.data_as(u64p), ferr.ctypes.data_as(u32p),
+                                           lvl.ctypes.data_as(u32p))
+        if rc:
+            raise RxError(rc, "selenite_rx_get_fskdec")
+        return text, count, ferr, lvl
+
+    def fsk_text(self, channel=None):
+        """the last min(count, ring) characters of a channel in order, as str; channel=None: a list for all channels.  Drains the stream."""
+        text, count, _, _ = self.fskdec()
+        out = [ring_text(text[c], int(count[c])) for c in (range(self.cfg.channels) if channel is None else [channel])]
+        return out if channel is None else out[0]
+
+    def fsk_lvl(self):
+        """the level of every channel behind the last tick, uint32 [channels]: 1 = mark (idle), 0 = space; drains the stream"""
+        return self.fskdec()[3]
+
+    def fskdec_text_device(self):
+        """device address of the rings, u8 [channels][ring] (None while the stage is off)"""
+        return self.L.selenite_rx_fskdec_text_device(self.h)
+
+    def fskdec_count_device(self):
+        """device address of the count row, u64 [channels] (None while the stage is off)"""
+        return self.L.selenite_rx_fskdec_count_device(self.h)
+
+    def fskdec_lvl_device(self):
+        """device address of the lvl row, u32 [channels] (None while the stage is off)"""
+        return self.L.selenite_rx_fskdec_lvl_device(self.h)
 
     def close(self):
         if self.h:
